@@ -9,18 +9,24 @@ HBM before the timed region and the reconstructed (timestamp, value) columns are
 
 `python bench.py --gpus N` starts the N ranks itself when it is not already one of them (a child
 `python -m torch.distributed.run`, started before this process touches a GPU; its JSON line is
-relayed and its exit code returned). With N = 1 the single rank still joins a 1-rank process group
-and an RCCL communicator of the C ABI (mdb_comm_init), so the final aggregate merge - the one
-exchange step of the path - runs over RCCL on every box.
+relayed and its exit code returned). With N = 1 the single rank still joins a 1-rank process group;
+under --full it also makes an RCCL communicator of the C ABI (mdb_comm_init), so the final aggregate
+merge - the one exchange step of the path - runs over RCCL on every box.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` for the dominant
-kernel (k_grid_tiles: algorithmic bytes / HIP-event time measured on the launch stream),
-`cpu_baseline` (the CPU oracle, a port of the reference's per-row GridStream loop, timed on the host
-cores on a bounded sample of the same segments) and `verified`: what the run compared with the
-oracle AFTER the timed region (the fitted segments of the sample series byte for byte, the
-reconstructed columns of the sample bit for bit).
+Prints ONE JSON line on rank 0 (the contract's keys first). A plain run sets up, warms up,
+times the K steps and reports them; everything else is measured or checked under `--full` only:
+`roofline` for the dominant kernel (k_grid_tiles: algorithmic bytes / HIP-event time measured on
+the launch stream), `cpu_baseline` (the CPU oracle, a port of the reference's per-row GridStream
+loop, timed on the host cores on a bounded sample of the same segments), `verified`: what the run
+compared with the oracle AFTER the timed region (the fitted segments of the sample series byte for
+byte, the reconstructed columns of the sample bit for bit), the aggregates and their merge over
+RCCL, and the secondary blocks (host path, irregular timestamps, mixed models).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--series S] [--points P]
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 / float64,
+a fixed sample of the rank-0 output) so that two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--series S] [--points P] [--full]
+                       [--dump-outputs DIR]
 """
 
 import argparse
@@ -45,6 +51,13 @@ INTERVAL_US = 1000
 GRID_KERNEL_SOURCES = ("mdb_grid.hip", "mdb_segment_dev.hpp", "mdb_common.hpp")
 FIT_KERNEL_SOURCES = ("mdb_fit.hip", "mdb_segment_dev.hpp", "mdb_common.hpp")
 SHADER_CLOCK_MHZ = 2400.0  # hipDeviceAttributeClockRate of the MI355X (s_memtime against the host clock: 2.37-2.40 GHz under load)
+# --dump-outputs: a fixed sample of a large output - runs of consecutive items at places drawn from DUMP_SEED - held
+# to DUMP_LIMIT_BYTES in all
+DUMP_SEED = 0x4D44425F44554D50
+DUMP_BLOCKS = 256
+GRID_DUMP_POINTS = 1 << 20     # 20 B a point: timestamp and index as f64, value as f32
+FIT_DUMP_ROWS = 1 << 16        # segment rows, with their payload bytes
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse_args():
@@ -87,6 +100,11 @@ def parse_args():
                              "beside bench.py); stdout carries the compact line only")
     parser.add_argument("--fit-repetitions", type=int, default=5,
                         help="timed repetitions of every fit that is not the timed step (median, min, max reported)")
+    parser.add_argument("--full", action="store_true",
+                        help="also measure and check everything besides the timed steps: rooflines, aggregates and their "
+                             "RCCL merge, CPU baselines, verification against the oracle, secondary blocks")
+    parser.add_argument("--dump-outputs", default=None, metavar="DIR",
+                        help="after the timed steps, write what the last one computed to DIR/<name>.npy")
     return parser.parse_args()
 
 
@@ -207,6 +225,33 @@ def spread(seconds):
     return {"median": statistics.median(seconds), "min": min(seconds), "max": max(seconds), "repetitions": len(seconds)}
 
 
+def dump_blocks(np, n, items):
+    """(start, count) of the runs of an n-item output that --dump-outputs writes: all of it when it holds at most
+    `items`, else DUMP_BLOCKS runs of items / DUMP_BLOCKS consecutive items - the first, the last and the others at
+    places drawn from DUMP_SEED - in order. The same n gives the same runs in every run."""
+    if n <= items:
+        return [(0, n)]
+    width = items // DUMP_BLOCKS
+    slots = n // width
+    drawn = np.random.default_rng(DUMP_SEED).choice(slots - 2, size=DUMP_BLOCKS - 2, replace=False)
+    starts = sorted((int(slot) + 1) * width for slot in drawn)
+    return [(0, width)] + [(start, width) for start in starts] + [(n - width, width)]
+
+
+def write_outputs(directory, arrays):
+    """DIR/<name>.npy of every array (float32 / float64 only), refused as a whole when over DUMP_LIMIT_BYTES."""
+    import numpy as np
+    total = sum(array.nbytes for array in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, over the {DUMP_LIMIT_BYTES} they are held to")
+    os.makedirs(directory, exist_ok=True)
+    for name, array in arrays.items():
+        if array.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"--dump-outputs: {name} is {array.dtype}, not float32 / float64")
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(array))
+    print(f"[bench] outputs: {len(arrays)} arrays, {total} bytes in {directory}", file=sys.stderr, flush=True)
+
+
 def timed_fit(context, call, repetitions):
     """`call()` (a fit that returns device segments) once untimed - the context's scratch grows -, then `repetitions`
     times under the wall clock with the kernels' HIP-event times; returns (segments of the last call, seconds[],
@@ -233,7 +278,8 @@ def fit_on_gpu(context, mdb, np, args, rank, keep_series):
     """Generate this rank's series on the device and compress them with the HIP fitter, in groups of
     series so that raw values never need more than a few GB of HBM at once. Returns the device
     batches, the wall-clock seconds of every repetition (summed over the groups) with the mean HIP-event
-    time of every fit kernel, and the raw values of the first `keep_series` series exactly as the fitter read them."""
+    time of every fit kernel (under --full only: a plain run fits once, untimed), and the raw values of the first
+    `keep_series` series exactly as the fitter read them."""
     eb = mdb.error_bound("relative", args.error_bound)
     chunks_per_series = (args.points + CHUNK_POINTS - 1) // CHUNK_POINTS
     # All series of the rank in one launch when they fit (one lane per chunk: occupancy = chunks).
@@ -252,9 +298,13 @@ def fit_on_gpu(context, mdb, np, args, rank, keep_series):
         k = n_series * chunks_per_series
         offsets_dev = context.upload_array(offsets)
         first_index_dev = context.upload_array(first_index)
-        segments, seconds, kernels = timed_fit(
-            context, lambda: context.compress_chunks_dev(0, values, offsets_dev, k, eb, 0, INTERVAL_US, first_index_dev),
-            args.fit_repetitions)
+        def fit():
+            return context.compress_chunks_dev(0, values, offsets_dev, k, eb, 0, INTERVAL_US, first_index_dev)
+        if args.full:
+            segments, seconds, kernels = timed_fit(context, fit, args.fit_repetitions)
+        else:  # (a plain run: the segments the timed step grids, the fit itself is not measured)
+            segments, seconds, kernels = fit(), [], {}
+            context.sync()
         parts.append(segments)
         fit_seconds = seconds if fit_seconds is None else [a + b for a, b in zip(fit_seconds, seconds)]
         for name, ms in kernels.items():
@@ -818,9 +868,10 @@ class GpuWorkload:
         self.np, self.mdb = np, mdb
         self.context = mdb.Context(local_rank)
         self.info = self.context.device_info()
-        with phase("comm_init"):
-            sharding.init_comm(self.context, dist)  # the C ABI's own RCCL communicator (mdb_comm_init)
-        self.verify = rank == 0 and not args.no_cpu_baseline
+        if args.full:  # (the aggregates' merge is the communicator's one user)
+            with phase("comm_init"):
+                sharding.init_comm(self.context, dist)  # the C ABI's own RCCL communicator (mdb_comm_init)
+        self.verify = rank == 0 and args.full and not args.no_cpu_baseline
         self.parts, self.out_ts, self.out_val = [], None, None
 
     def sync(self):
@@ -872,7 +923,8 @@ class GpuWorkload:
         total_points, n_segments, out_ts, out_val = self.total_points, self.n_segments, self.out_ts, self.out_val
         assert ranged or self.produced == total_points
         points_per_step = self.produced
-        metrics = self.metrics
+        if not args.full:  # a plain run: the timed steps' figure alone
+            return self.headline(elapsed, per_rank_seconds, points_per_step) if rank == 0 else None
 
         # ---- roofline of the dominant kernel: HIP events on the launch stream ------------------------
         context.profile_enable(True)
@@ -1081,41 +1133,11 @@ class GpuWorkload:
                 with phase("mixed_models"):
                     mixed_result = mixed_models(context, mdb, np, ora, args)
 
-        value = world * points_per_step * args.steps / elapsed
         fit_kernel_ms, fit_points, fit_timings = self.fit_kernel_ms, self.fit_points, self.fit_seconds
         fit_seconds = statistics.median(fit_timings)
         return {
-            "metric": "gridded values/sec",
-            "value": value,
-            "unit": "values/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
+            **self.headline(elapsed, per_rank_seconds, points_per_step),
             "rccl_ranks_seen": ranks_seen,
-            "ms_per_step_per_rank": {"min": 1e3 * min(per_rank_seconds) / args.steps,
-                                     "max": 1e3 * max(per_rank_seconds) / args.steps},
-            "config": {
-                "workload": f"{args.series} series x {args.points} points sine+noise, "
-                            f"relative error bound {args.error_bound} %, grid() decode of the "
-                            f"segments to (timestamp i64, value f32) columns in HBM, per GPU"
-                            + (f"; point-range query over the middle {args.range_middle:g} of the time axis "
-                               f"({points_per_step} points per step)" if ranged else ""),
-                "series_per_gpu": args.series,
-                "points_per_series": args.points,
-                "segments_per_gpu": n_segments,
-                "segment_mix": metrics,
-                "parallelism": f"series-sharded x{world}, no data-path collective",
-                "arithmetic": "Swing values as (f64 slope * f64 t + f64 intercept) -> f32, timestamps i64; "
-                              "output columns i64 + f32 (12 B/point)",
-                "device": self.info["name"],
-                "libraries": loaded_runtime_libraries(),
-            },
             "roofline": {
                 "bound": "hbm",
                 "kernel": "k_grid_tiles",
@@ -1151,6 +1173,55 @@ class GpuWorkload:
             },
         }
 
+    def headline(self, elapsed, per_rank_seconds, points_per_step):
+        """The line's contract keys and `config`: what the timed steps did and how fast."""
+        args, world = self.args, self.world
+        return {
+            "metric": "gridded values/sec",
+            "value": world * points_per_step * args.steps / elapsed,
+            "unit": "values/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "full": bool(args.full),
+            "ms_per_step_per_rank": {"min": 1e3 * min(per_rank_seconds) / args.steps,
+                                     "max": 1e3 * max(per_rank_seconds) / args.steps},
+            "config": {
+                "workload": f"{args.series} series x {args.points} points sine+noise, "
+                            f"relative error bound {args.error_bound} %, grid() decode of the "
+                            f"segments to (timestamp i64, value f32) columns in HBM, per GPU"
+                            + (f"; point-range query over the middle {args.range_middle:g} of the time axis "
+                               f"({points_per_step} points per step)" if self.ranged else ""),
+                "series_per_gpu": args.series,
+                "points_per_series": args.points,
+                "segments_per_gpu": self.n_segments,
+                "segment_mix": self.metrics,
+                "parallelism": f"series-sharded x{world}, no data-path collective",
+                "arithmetic": "Swing values as (f64 slope * f64 t + f64 intercept) -> f32, timestamps i64; "
+                              "output columns i64 + f32 (12 B/point)",
+                "device": self.info["name"],
+                "libraries": loaded_runtime_libraries(),
+            },
+            "phases_s": {name: round(seconds, 2) for name, seconds in PHASES.items()},
+        }
+
+    def outputs(self):
+        """What a caller of the timed step receives - the (timestamp, value) columns it wrote - for a fixed sample of
+        the points (dump_blocks)."""
+        np, context, n = self.np, self.context, self.produced
+        blocks = dump_blocks(np, n, GRID_DUMP_POINTS)
+        ts = np.concatenate([context.download_array(self.out_ts, count, np.int64, offset_elements=at) for at, count in blocks])
+        values = np.concatenate([context.download_array(self.out_val, count, np.float32, offset_elements=at)
+                                 for at, count in blocks])
+        index = np.concatenate([np.arange(at, at + count) for at, count in blocks])
+        return {"grid_point_index": index.astype(np.float64), "grid_timestamps": ts.astype(np.float64), "grid_values": values}
+
     def free_headline_buffers(self):
         for part in self.parts:
             part.free()
@@ -1181,9 +1252,10 @@ class FitWorkload:
         self.np, self.mdb = np, mdb
         self.context = mdb.Context(local_rank)
         self.info = self.context.device_info()
-        with phase("comm_init"):
-            sharding.init_comm(self.context, dist)
-        self.verify = rank == 0 and not args.no_cpu_baseline
+        if args.full:
+            with phase("comm_init"):
+                sharding.init_comm(self.context, dist)
+        self.verify = rank == 0 and args.full and not args.no_cpu_baseline
         self.values = self.offsets_dev = self.first_index_dev = self.segments = None
 
     def sync(self):
@@ -1224,6 +1296,8 @@ class FitWorkload:
         args, context, np, mdb = self.args, self.context, self.np, self.mdb
         rank, world = self.rank, self.world
         n_segments = len(self.segments)
+        if not args.full:  # a plain run: the timed steps' figure alone
+            return self.headline(elapsed, per_rank_seconds, n_segments) if rank == 0 else None
         # ---- the kernels of a step: HIP events on the launch stream ------------------------------------
         context.profile_enable(True)
         context.profile_reset()
@@ -1263,11 +1337,27 @@ class FitWorkload:
                         "how": "after the timed region: the oracle's fit of the sample series' exact bytes == the segments "
                                "of the last timed step (all columns, bit patterns); the segments of the rank hold exactly "
                                "the points that were fitted (mdb_grid_count); device generator == host definition"}
-        value = world * self.total * args.steps / elapsed
-        mix = context.grid_count_dev(self.segments)
+        line = self.headline(elapsed, per_rank_seconds, n_segments)
+        line["config"]["points_in_segments"] = context.grid_count_dev(self.segments)
+        return {
+            **line,
+            "rccl_ranks_seen": ranks_seen,
+            "roofline": fit_roofline(kernel_ms, self.total, self.info),
+            "kernels_ms": {name: round(ms, 3) for name, ms in kernel_ms.items()},
+            "call_ms": {"median": 1e3 * statistics.median(call_seconds), "min": 1e3 * min(call_seconds),
+                        "max": 1e3 * max(call_seconds)},
+            "cpu_baseline": cpu_baseline,
+            "verified": verified,
+            "aggregates_of_fitted_segments": {"count": state.count, "min": state.min, "max": state.max, "sum": state.sum},
+            "phases_s": {name: round(seconds, 2) for name, seconds in PHASES.items()},
+        }
+
+    def headline(self, elapsed, per_rank_seconds, n_segments):
+        """The line's contract keys and `config`: what the timed steps did and how fast."""
+        args, world = self.args, self.world
         return {
             "metric": "fit points/sec",
-            "value": value,
+            "value": world * self.total * args.steps / elapsed,
             "unit": "points/s",
             "n_gpus": world,
             "steps": args.steps,
@@ -1278,7 +1368,7 @@ class FitWorkload:
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
-            "rccl_ranks_seen": ranks_seen,
+            "full": bool(args.full),
             "segments_per_s": world * n_segments * args.steps / elapsed,
             "ms_per_step_per_rank": {"min": 1e3 * min(per_rank_seconds) / args.steps,
                                      "max": 1e3 * max(per_rank_seconds) / args.steps},
@@ -1290,21 +1380,33 @@ class FitWorkload:
                 "points_per_series": args.points,
                 "chunks_per_gpu": self.n_chunks,
                 "segments_per_gpu": n_segments,
-                "points_in_segments": mix,
                 "parallelism": f"series-sharded x{world}, no data-path collective",
                 "arithmetic": "Swing in f64 (no contraction), PMC-Mean f64 sum / f32 tests, MacaqueV u32 bit streams",
                 "device": self.info["name"],
                 "libraries": loaded_runtime_libraries(),
             },
-            "roofline": fit_roofline(kernel_ms, self.total, self.info),
-            "kernels_ms": {name: round(ms, 3) for name, ms in kernel_ms.items()},
-            "call_ms": {"median": 1e3 * statistics.median(call_seconds), "min": 1e3 * min(call_seconds),
-                        "max": 1e3 * max(call_seconds)},
-            "cpu_baseline": cpu_baseline,
-            "verified": verified,
-            "aggregates_of_fitted_segments": {"count": state.count, "min": state.min, "max": state.max, "sum": state.sum},
             "phases_s": {name: round(seconds, 2) for name, seconds in PHASES.items()},
         }
+
+    def outputs(self):
+        """What a caller of the timed step receives - the segment columns it wrote - for a fixed sample of rows: the
+        fixed-width columns, and of every binary column (timestamps, values, residuals) the rows' lengths and their
+        bytes one after the other."""
+        np = self.np
+        batch = self.segments.download()
+        rows = np.concatenate([np.arange(at, at + count) for at, count in dump_blocks(np, len(batch), FIT_DUMP_ROWS)])
+        sample = batch.take(rows)
+        arrays = {"segment_row_index": rows.astype(np.float64),
+                  "segment_model_type_id": sample.model_type_id.astype(np.float64),
+                  "segment_start_time": sample.start_time.astype(np.float64),
+                  "segment_end_time": sample.end_time.astype(np.float64),
+                  "segment_min_value": sample.min_value,
+                  "segment_max_value": sample.max_value}
+        for name in ("timestamps", "values", "residuals"):
+            column = getattr(sample, name)
+            arrays[f"segment_{name}_lengths"] = column.lengths().astype(np.float64)
+            arrays[f"segment_{name}_bytes"] = np.frombuffer(b"".join(column.to_bytes_list()), dtype=np.uint8).astype(np.float32)
+        return arrays
 
     def close(self):
         if self.segments is not None:
@@ -1517,6 +1619,13 @@ def orchestrate(args, make_workload, backend="nccl", result_fd=1):
         t = torch.tensor([own_elapsed], dtype=torch.float64)
         gathered = [torch.zeros_like(t) for _ in range(world)]
         attempt(lambda: dist.all_gather(gathered, t, group=control))
+        everyone_fine = checkpoint()
+    if everyone_fine and getattr(args, "dump_outputs", None):
+        # What the last timed step computed, before the report runs anything else (rank 0's share of the output);
+        # every rank meets at the checkpoint behind it.
+        if rank == 0:
+            with phase("dump_outputs"):
+                attempt(lambda: write_outputs(args.dump_outputs, workload_box[0].outputs()))
         everyone_fine = checkpoint()
     if everyone_fine:
         per_rank_seconds = [float(x.item()) for x in gathered]

@@ -18,7 +18,7 @@ timeout 600 python3 scripts/r04/segment_files_e2e.py > $OUT/segment_files_e2e.lo
 timeout 600 python3 scripts/profile_irregular.py > $OUT/irregular.log 2>&1; echo "irregular rc=$?"
 timeout 600 python3 scripts/r04/tail_lengths.py > $OUT/tail_lengths.log 2>&1; echo "tail lengths rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_mixed -o mixed -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-irregular --no-cpu-baseline > $OUT/prof_mixed.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_mixed -o mixed -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-irregular --no-cpu-baseline > $OUT/prof_mixed.log 2>&1
 echo "mixed trace rc=$?"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_fit_latency -o fit_latency -- python3 $ROOT/scripts/r04/fit_latency.py > $OUT/prof_fit_latency.log 2>&1
 echo "fit latency trace rc=$?"

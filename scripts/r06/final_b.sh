@@ -18,7 +18,7 @@ timeout 600 python3 scripts/r06/lossless_long_chunk.py > $OUT/lossless_long_chun
 timeout 600 python3 scripts/profile_irregular.py > $OUT/irregular.log 2>&1; echo "irregular rc=$?"
 bash scripts/pmc_kernel.sh k_fit_models_wave scripts/r04/mixed_fit.py 1e9 lossless > $OUT/pmc_wave_lossless.log 2>&1; echo "pmc wave rc=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_mixed -o mixed -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-irregular --no-cpu-baseline --detail-file $OUT/prof_mixed_detail.json > $OUT/prof_mixed.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_mixed -o mixed -- python3 $ROOT/bench.py --full --steps 1 --warmup 0 --no-irregular --no-cpu-baseline --detail-file $OUT/prof_mixed_detail.json > $OUT/prof_mixed.log 2>&1
 echo "mixed trace rc=$?"
 find $ROOT/gpurun_out -name "*.csv" -size +20M -delete
 for f in fit_latency mixed_fit mixed_fit_wave_counts mixed_grid lossless_long_chunk pmc_wave_lossless; do echo "== $f"; tail -n 8 $OUT/$f.log | cut -c1-400; done

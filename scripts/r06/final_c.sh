@@ -6,7 +6,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/r06
 mkdir -p $OUT
 cd $ROOT
-run() { name=$1; shift; python3 bench.py --detail-file $OUT/${name}_detail.json "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$? bytes=$(wc -c < $OUT/$name.json)"; }
+run() { name=$1; shift; python3 bench.py --full --detail-file $OUT/${name}_detail.json "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "$name rc=$? bytes=$(wc -c < $OUT/$name.json)"; }
 run bench_default
 run bench_timed_fit --timed fit
 run bench_config4_shape_1gpu --series 12500 --points 1000000

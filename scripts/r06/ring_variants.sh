@@ -9,6 +9,6 @@ for v in product ring12 ring16; do
   [ $v = product ] && lib=modelardb-rs_amd/csrc/libmdb_hip.so
   echo "== $v" >> $out
   MDB_HIP_LIBRARY=$PWD/$lib timeout 200 python3 scripts/r04/mixed_fit.py 1e9 rel1 2>&1 | grep "^rel1" | cut -c1-420 >> $out
-  MDB_HIP_LIBRARY=$PWD/$lib timeout 300 python3 bench.py --timed fit --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --detail-file /tmp/d.json 2>/dev/null | python3 -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('headline fit', round(b['ms_per_step'],2), 'ms/step, kernel', round(b['roofline']['kernel_ms'],2))" >> $out 2>&1
+  MDB_HIP_LIBRARY=$PWD/$lib timeout 300 python3 bench.py --full --timed fit --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --detail-file "${out%.txt}_detail.json" 2>/dev/null | python3 -c "import sys,json; b=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('headline fit', round(b['ms_per_step'],2), 'ms/step, kernel', round(b['roofline']['kernel_ms'],2))" >> $out 2>&1
 done
 cat $out

@@ -106,40 +106,95 @@ def test_rust_binding_declares_every_symbol():
         assert re.search(rf"pub fn {name}\(", rust), f"sys.rs does not declare {name}"
 
 
-def test_rust_patches_apply_to_the_reference():
-    """The three call-site patches apply cleanly to the reference tree (present in the authoring
-    container only; nothing at run time reads it)."""
+PATCH_TARGETS = os.path.join(REPO_ROOT, "tests", "golden", "reference_patch_targets.json")
+
+
+def _patches():
     import glob
+    return sorted(glob.glob(os.path.join(REPO_ROOT, "rust", "patches", "*.patch")))
+
+
+def _hunks(patch):
+    """[(path, old_start, old_lines, [pre-image lines])] of a unified diff, in order."""
+    hunks, path, lines = [], None, open(patch).read().split("\n")
+    i = 0
+    while i < len(lines):
+        if lines[i].startswith("--- a/") and i + 1 < len(lines) and lines[i + 1].startswith("+++ b/"):
+            path, i = lines[i][len("--- a/"):], i + 2
+            continue
+        head = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", lines[i])
+        if not head:
+            i += 1
+            continue
+        old_start, old_lines = int(head.group(1)), int(head.group(2) or 1)
+        new_lines = int(head.group(4) or 1)
+        pre, seen_old, seen_new, i = [], 0, 0, i + 1
+        while seen_old < old_lines or seen_new < new_lines:
+            line = lines[i]
+            kind, text = (line[:1] or " "), line[1:]
+            if kind in " -":
+                pre.append(text)
+                seen_old += 1
+            if kind in " +":
+                seen_new += 1
+            i += 1
+        hunks.append((path, old_start, old_lines, pre))
+    return hunks
+
+
+def _digest(lines):
+    import hashlib
+    return hashlib.sha256("\n".join(lines).encode()).hexdigest()
+
+
+def _pre_image_tree(root):
+    """The files the patches touch, as the reference holds them wherever a patch looks: every hunk's pre-image at its
+    line, checked against the fingerprints of the reference tree the patches were made against
+    (tests/golden/reference_patch_targets.json: each file's length and the SHA-256 of each hunk's lines); the lines no
+    patch looks at are placeholders."""
+    import json
+    targets = json.load(open(PATCH_TARGETS))["files"]
+    files = {}
+    for patch in _patches():
+        for path, old_start, old_lines, pre in _hunks(patch):
+            assert path in targets, f"{os.path.basename(patch)} touches {path}, which has no fingerprint"
+            target = targets[path]
+            if path not in files:
+                files[path] = [f"// line {n + 1} of {path}, which no patch looks at" for n in range(target["lines"])]
+            assert [old_start, old_lines, _digest(pre)] in target["hunks"], \
+                f"{os.path.basename(patch)}: the hunk at {path}:{old_start} is not what the reference holds there"
+            files[path][old_start - 1:old_start - 1 + old_lines] = pre
+    for path, lines in files.items():
+        os.makedirs(os.path.dirname(os.path.join(root, path)), exist_ok=True)
+        with open(os.path.join(root, path), "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return files
+
+
+def test_rust_patches_apply_to_the_reference(tmp_path):
+    """The four call-site patches apply cleanly to the reference tree they were made against, rebuilt from the patches
+    and the tree's recorded fingerprints (_pre_image_tree)."""
     import subprocess
-    reference = "/root/reference"
-    if not os.path.isdir(os.path.join(reference, "crates")):
-        pytest.skip("the reference tree is not present")
-    patches = sorted(glob.glob(os.path.join(REPO_ROOT, "rust", "patches", "*.patch")))
+    patches = _patches()
     assert len(patches) == 4
+    _pre_image_tree(tmp_path)
     for patch in patches:
         with open(patch) as f:
-            done = subprocess.run(["patch", "-p1", "--dry-run", "--force", "-d", reference], stdin=f,
+            done = subprocess.run(["patch", "-p1", "--dry-run", "--force", "-d", str(tmp_path)], stdin=f,
                                   capture_output=True, text=True)
         assert done.returncode == 0, done.stdout + done.stderr
         assert "FAILED" not in done.stdout and "fuzz" not in done.stdout, done.stdout
 
 
 def test_patched_crates_depend_on_the_binding_they_use(tmp_path):
-    """The four patches applied IN SEQUENCE to a copy of the crates they touch (no toolchain can compile the result
-    here, so what can be checked is checked): every patch applies on top of the ones before it without fuzz, every crate
-    whose patched sources name `modelardb_hip::` lists the crate in its Cargo.toml, and every function of the binding
-    the patched sources call exists in rust/modelardb_hip/src/lib.rs."""
-    import glob
-    import shutil
+    """The four patches applied IN SEQUENCE to the files of the reference they touch (rebuilt by _pre_image_tree; no
+    toolchain can compile the result here, so what can be checked is checked): every patch applies on top of the ones
+    before it without fuzz, every crate whose patched sources name `modelardb_hip::` lists the crate in its Cargo.toml,
+    and every function of the binding the patched sources call exists in rust/modelardb_hip/src/lib.rs."""
     import subprocess
-    reference = "/root/reference"
-    if not os.path.isdir(os.path.join(reference, "crates")):
-        pytest.skip("the reference tree is not present")
     crates = ("modelardb_storage", "modelardb_compression", "modelardb_server")
-    for crate in crates:
-        shutil.copytree(os.path.join(reference, "crates", crate), tmp_path / "crates" / crate,
-                        ignore=shutil.ignore_patterns("target"))
-    for patch in sorted(glob.glob(os.path.join(REPO_ROOT, "rust", "patches", "*.patch"))):
+    _pre_image_tree(tmp_path)
+    for patch in _patches():
         with open(patch) as f:
             done = subprocess.run(["patch", "-p1", "--force", "-d", str(tmp_path)], stdin=f, capture_output=True, text=True)
         assert done.returncode == 0, done.stdout + done.stderr
@@ -165,6 +220,23 @@ def test_patched_crates_depend_on_the_binding_they_use(tmp_path):
                 if f".{method}(" in source:
                     assert re.search(rf"pub fn {method}\(", binding), f"{crate} calls .{method}(), which the binding lacks"
     assert users == 3
+
+
+def record_patch_targets(tree):
+    """tests/golden/reference_patch_targets.json from a ModelarDB-RS checkout at `tree` that the patches apply to:
+    `python tests/test_abi_cpu.py TREE`. Fingerprints only - no line of the tree is stored."""
+    import json
+    files = {}
+    for patch in _patches():
+        for path, old_start, old_lines, _ in _hunks(patch):
+            lines = open(os.path.join(tree, path)).read().split("\n")[:-1]
+            target = files.setdefault(path, {"lines": len(lines), "hunks": []})
+            target["hunks"].append([old_start, old_lines, _digest(lines[old_start - 1:old_start - 1 + old_lines])])
+    with open(PATCH_TARGETS, "w") as f:
+        json.dump({"_comment": "the files of the ModelarDB-RS tree that rust/patches/ apply to: their number of lines "
+                               "and, for every hunk, [first line, lines, SHA-256 of those lines joined by newlines]",
+                   "files": files}, f, indent=1)
+        f.write("\n")
 
 
 def test_version_string():
@@ -270,3 +342,8 @@ def test_switches_are_read_from_the_environment_once_and_set_without_it(monkeypa
     monkeypatch.delenv("MDB_TEST_SWITCH")
     assert library.mdb_reload_options() == 0
     assert library.mdb_option(b"MDB_TEST_SWITCH") is None
+
+
+if __name__ == "__main__":
+    import sys
+    record_patch_targets(sys.argv[1])

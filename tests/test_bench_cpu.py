@@ -145,3 +145,39 @@ def test_a_failing_rank_ends_the_job_non_zero_without_a_line(fail_on):
     assert done.returncode != 0
     assert not [line for line in done.stdout.splitlines() if line.startswith("{")]
     assert "asked to" in done.stderr
+
+
+def test_a_plain_run_measures_the_timed_steps_alone(monkeypatch):
+    """Everything besides the timed steps is behind --full, off by default; outputs are written only when asked."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse_args()
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "out"
+
+
+@pytest.mark.parametrize("n, items", [(10 ** 10, bench.GRID_DUMP_POINTS), (13_464_195, bench.FIT_DUMP_ROWS),
+                                      (bench.GRID_DUMP_POINTS + 1, bench.GRID_DUMP_POINTS), (100, 4096), (0, 4096)])
+def test_the_dumped_sample_is_fixed_and_inside_the_output(n, items):
+    import numpy as np
+    blocks = bench.dump_blocks(np, n, items)
+    assert blocks == bench.dump_blocks(np, n, items)             # the same runs in every run
+    assert sum(count for _, count in blocks) == min(n, items)
+    assert blocks[0][0] == 0 and blocks[-1][0] + blocks[-1][1] == n
+    for (start, count), (following, _) in zip(blocks, blocks[1:]):
+        assert start + count <= following                         # in order, no run twice
+
+
+def test_outputs_are_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    arrays = {"grid_timestamps": np.arange(10, dtype=np.float64), "grid_values": np.ones(10, dtype=np.float32)}
+    bench.write_outputs(str(tmp_path / "dump"), arrays)
+    for name, array in arrays.items():
+        loaded = np.load(tmp_path / "dump" / f"{name}.npy")
+        assert loaded.dtype == array.dtype and np.array_equal(loaded, array)
+    with pytest.raises(SystemExit, match="float32"):
+        bench.write_outputs(str(tmp_path / "ints"), {"ids": np.arange(3)})
+    with pytest.raises(SystemExit, match="bytes"):
+        bench.write_outputs(str(tmp_path / "large"), {"big": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "large").exists()

@@ -1,7 +1,7 @@
 """The final aggregate merge behind the C ABI (mdb_comm_init / mdb_agg_all_reduce) on
 one GPU: a communicator of world size 1 over RCCL. The fold rule itself (rank order, the
 accumulators' update rules) is covered on CPU by tests/test_sharding_cpu.py through mdb_agg_merge;
-world size 2 runs under `bench.py --gpus 2` on a multi-GPU node."""
+world size 2 runs under `bench.py --gpus 2 --full` on a multi-GPU node."""
 
 import numpy as np
 import pytest
