@@ -232,6 +232,37 @@ int mdb_agg_batch_range_dev(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, 
 int mdb_agg_batch_range_list(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs, int64_t t_lo,
                              int64_t t_hi, uint32_t which_mask, mdb_agg_state *inout);
 
+/* Extension: the aggregates per time bucket and group - what the reference computes for
+ * SELECT <tags>, date_bin(width, ts, origin), COUNT/MIN/MAX/SUM/AVG(field) ... GROUP BY 1, 2 with GridExec, the
+ * date_bin / range filter and AggregateExec (its model-based rule only takes an empty GROUP BY,
+ * model_simple_aggregates.rs:219), computed on the segments without materialising a point.
+ *   inout: row-major [n_groups][n_buckets] states. Each cell is folded with the rules of mdb_agg_merge, for the
+ *     aggregates in request->which_mask as mdb_agg_batch folds them; a cell with no points is left exactly as it
+ *     was (a fresh cell stays {0, 0, FLT_MAX, -FLT_MAX}).
+ *   group_of_segment: one group id per segment row (the caller derives it from the tag columns: one id per series
+ *     or per tag combination); NULL puts every segment in group 0. The list form takes one such array per input
+ *     (NULL, or a NULL entry: group 0).
+ *   Parity: the reference's fallback plan (GridExec -> date_bin / range filter -> GROUP BY). COUNT, MIN and MAX are
+ *     exact; SUM is the f64 sum of a cell's f32 points, within the 0.001 % of the other aggregates.
+ *   Determinism: for the same input, request and form (host, dev or list), results are bit-identical from run to
+ *     run, and the three forms agree bit for bit; no float atomics. MDB_AGG_BUCKET_SLICE_PAIRS
+ *     changes the order in which a cell's partials are added, within the tolerance.
+ *   Errors (mdb_last_error set, inout untouched): width <= 0, n_groups == 0, n_groups * n_buckets overflowing,
+ *     a group id >= n_groups (every row is checked), a malformed segment among those the request reaches (the error
+ *     classes of mdb_agg_batch). As for mdb_agg_batch_range, a segment outside every bucket or outside
+ *     [t_lo, t_hi] is not examined: the reference's scan prunes such segments on start_time / end_time too.
+ *   n_buckets == 0 (or an empty batch) does nothing and succeeds. Bucket arithmetic does not overflow for any
+ *     origin, width, t_lo or t_hi. */
+int mdb_agg_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                    const mdb_bucket_request *request, mdb_agg_state *inout);
+/* All device pointers: the segments, group_of_segment and inout are in HBM. */
+int mdb_agg_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                        const mdb_bucket_request *request, mdb_agg_state *inout);
+/* Several host batches (rows in the order of the list) folded as one batch, as mdb_agg_batch_list does. */
+int mdb_agg_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs,
+                         const uint32_t *const *group_of_segment, uint32_t n_inputs,
+                         const mdb_bucket_request *request, mdb_agg_state *inout);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through
@@ -311,6 +342,9 @@ int mdb_comm_close(mdb_ctx *ctx); /* also done by mdb_close */
 int mdb_agg_all_reduce(mdb_ctx *ctx, mdb_agg_state *inout, int32_t *ranks_seen);
 /* The fold itself, for hosts that move the states themselves: into = merge(into, from). */
 int mdb_agg_merge(mdb_agg_state *into, const mdb_agg_state *from);
+/* The same for n states in a row: into[k] = merge(into[k], from[k]), k < n (host arithmetic, no context): the
+ * fold of two cell arrays of mdb_agg_buckets* that a host has moved itself. n == 0 succeeds. */
+int mdb_agg_merge_n(mdb_agg_state *into, const mdb_agg_state *from, uint64_t n);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 

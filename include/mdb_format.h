@@ -159,6 +159,17 @@ typedef struct mdb_grid_request {
     uint64_t reserve_front;  /* writable rows in front of every output column (the leftovers) */
 } mdb_grid_request;
 
+/* Buckets of date_bin(width, ts, origin) for mdb_agg_buckets*: bucket b holds the points with
+ * origin + b*width <= ts <= origin + (b+1)*width - 1, b = floor((ts - origin) / width) (floor, also for ts < origin). */
+typedef struct mdb_bucket_request {
+    int64_t  origin;
+    int64_t  width;       /* > 0, in the timestamps' unit (us) */
+    uint64_t n_buckets;   /* points outside buckets 0 .. n_buckets-1 are not counted */
+    int64_t  t_lo, t_hi;  /* inclusive time range ANDed with the buckets (INT64_MIN / INT64_MAX: none) */
+    uint32_t n_groups;    /* >= 1 */
+    uint32_t which_mask;  /* MDB_AGG_*, with the same meaning as in mdb_agg_batch */
+} mdb_bucket_request;     /* 48 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -229,5 +240,12 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_grid_request, reserve_front) == 24);
 MDB_LAYOUT_ASSERT(sizeof(mdb_chunk) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_chunk, values) == 8);
 MDB_LAYOUT_ASSERT(offsetof(mdb_chunk, n) == 16);
+MDB_LAYOUT_ASSERT(sizeof(mdb_bucket_request) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, width) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, n_buckets) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, t_lo) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, t_hi) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, n_groups) == 40);
+MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, which_mask) == 44);
 
 #endif /* MDB_FORMAT_H */

@@ -12,6 +12,6 @@ from ._abi import (  # noqa: F401
 )
 from .segments import BinaryViewColumn, SegmentBatch, error_bound  # noqa: F401
 from .api import (  # noqa: F401
-    Context, DeviceSegments, HipError, are_compressed_timestamps_regular, comm_unique_id,
-    is_value_within_error_bound,
+    AGG_STATE_DTYPE, Context, DeviceSegments, HipError, agg_merge_n, are_compressed_timestamps_regular,
+    comm_unique_id, fresh_agg_states, is_value_within_error_bound,
 )

@@ -141,6 +141,19 @@ class ChunkC(C.Structure):
     _fields_ = [("ts", C.c_void_p), ("values", C.c_void_p), ("n", C.c_uint64)]
 
 
+class BucketRequestC(C.Structure):
+    """mdb_bucket_request: the buckets of date_bin(width, ts, origin) for mdb_agg_buckets*."""
+    _fields_ = [
+        ("origin", C.c_int64),
+        ("width", C.c_int64),
+        ("n_buckets", C.c_uint64),
+        ("t_lo", C.c_int64),
+        ("t_hi", C.c_int64),
+        ("n_groups", C.c_uint32),
+        ("which_mask", C.c_uint32),
+    ]
+
+
 _HIP_SYMBOLS = {
     # name: (restype, argtypes)
     "mdb_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -202,6 +215,12 @@ _HIP_SYMBOLS = {
                                           C.c_uint32, C.POINTER(AggStateC)]),
     "mdb_agg_batch_range_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.c_uint32, C.c_int64,
                                            C.c_int64, C.c_uint32, C.POINTER(AggStateC)]),
+    "mdb_agg_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                  C.c_void_p]),
+    "mdb_agg_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                      C.c_void_p]),
+    "mdb_agg_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                       C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
     "mdb_compress_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, ErrorBoundC,
                                       C.POINTER(C.POINTER(SegmentsOwnedC))]),
     "mdb_compress_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
@@ -224,6 +243,7 @@ _HIP_SYMBOLS = {
     "mdb_comm_close": (C.c_int, [C.c_void_p]),
     "mdb_agg_all_reduce": (C.c_int, [C.c_void_p, C.POINTER(AggStateC), C.POINTER(C.c_int32)]),
     "mdb_agg_merge": (C.c_int, [C.POINTER(AggStateC), C.POINTER(AggStateC)]),
+    "mdb_agg_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "mdb_profile_reset": (C.c_int, [C.c_void_p]),
     "mdb_profile_get": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64),

@@ -110,6 +110,34 @@ def comm_unique_id():
     return buffer.raw
 
 
+# mdb_agg_state as a numpy record: the cells of mdb_agg_buckets*, row-major [n_groups][n_buckets].
+AGG_STATE_DTYPE = np.dtype([("sum", "<f8"), ("count", "<i8"), ("min", "<f4"), ("max", "<f4")])
+assert AGG_STATE_DTYPE.itemsize == C.sizeof(_abi.AggStateC)
+
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def fresh_agg_states(shape):
+    """Fresh states {0, 0, FLT_MAX, -FLT_MAX} (f32::MAX / f32::MIN, model_simple_aggregates.rs:413, 456)."""
+    states = np.zeros(shape, dtype=AGG_STATE_DTYPE)
+    states["min"] = _abi.F32_MAX
+    states["max"] = -_abi.F32_MAX
+    return states
+
+
+def agg_merge_n(into, other):
+    """into[k] = merge(into[k], other[k]) in place (mdb_agg_merge_n): two arrays of AGG_STATE_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != AGG_STATE_DTYPE or other.dtype != AGG_STATE_DTYPE or into.size != other.size:
+        raise ValueError("agg_merge_n takes two state arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("agg_merge_n merges into a contiguous array")
+    other = np.ascontiguousarray(other)
+    if lib.mdb_agg_merge_n(into.ctypes.data_as(C.c_void_p), other.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
 def is_value_within_error_bound(eb, real_value, approximate_value):
     """models/mod.rs:53-77 through the C ABI (host arithmetic, no GPU)."""
     lib = _abi.load_hip_library()
@@ -409,6 +437,85 @@ class Context:
         self._check(self.lib.mdb_agg_batch_range_dev(self.handle, C.byref(dev_segments.seg), t_lo,
                                                      t_hi, which_mask, C.byref(state)))
         return state
+
+    # ---- aggregates per time bucket ----------------------------------------------------------------
+
+    @staticmethod
+    def _bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, which_mask):
+        return _abi.BucketRequestC(int(origin), int(width), int(n_buckets), INT64_MIN if t_lo is None else int(t_lo),
+                                   INT64_MAX if t_hi is None else int(t_hi), int(n_groups), int(which_mask))
+
+    @staticmethod
+    def _bucket_states(states, n_groups, n_buckets):
+        if states is None:
+            return fresh_agg_states((n_groups, n_buckets))
+        if states.dtype != AGG_STATE_DTYPE or states.shape != (n_groups, n_buckets) or not states.flags.c_contiguous:
+            raise ValueError(f"states must be a contiguous ({n_groups}, {n_buckets}) array of AGG_STATE_DTYPE")
+        return states
+
+    @staticmethod
+    def _groups_array(groups, n_rows):
+        if groups is None:
+            return None
+        groups = np.ascontiguousarray(groups, dtype=np.uint32)
+        if groups.shape != (n_rows,):
+            raise ValueError(f"groups must hold one id per segment row ({n_rows})")
+        return groups
+
+    def agg_buckets(self, batch, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                    which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                    states=None, n_groups=None):
+        """COUNT / MIN / MAX / SUM per bucket of date_bin(width, ts, origin) and group (mdb_agg_buckets): returns
+        `states` (or fresh ones), shape (n_groups, n_buckets), folded in place. `groups`: one id per segment row
+        (None: all in group 0); n_groups defaults to states' rows, else to max(groups) + 1."""
+        return self.agg_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups], t_lo,
+                                     t_hi, which_mask, states, n_groups)
+
+    def agg_buckets_list(self, batches, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                         which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                         states=None, n_groups=None):
+        """Several host batches folded as one (mdb_agg_buckets_list); `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, states, batch_groups)
+        states = self._bucket_states(states, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, which_mask)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_agg_buckets_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                  states.ctypes.data_as(C.c_void_p)))
+        return states
+
+    def agg_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                        which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                        states=None, n_groups=None):
+        """mdb_agg_buckets_dev on a resident batch: `groups` and `states` are uploaded, the states downloaded again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, states, [groups])
+        states = self._bucket_states(states, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, which_mask)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_states = self.upload_array(states)
+        try:
+            self._check(self.lib.mdb_agg_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                     None if dev_groups is None else C.c_void_p(dev_groups),
+                                                     C.byref(request), C.c_void_p(dev_states)))
+            states[...] = self.download_array(dev_states, states.size, AGG_STATE_DTYPE).reshape(states.shape)
+        finally:
+            self.dev_free(dev_states)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return states
+
+    @staticmethod
+    def _n_groups(n_groups, states, groups):
+        if n_groups is not None:
+            return int(n_groups)
+        if states is not None:
+            return int(states.shape[0])
+        return max([int(g.max()) + 1 for g in groups if g is not None and g.size] or [1])
 
     # ---- fit -------------------------------------------------------------------------------------
 

@@ -12,6 +12,7 @@
 // k_agg_finish reduces the partials with one workgroup. The fixed tree makes SUM run-to-run
 // deterministic; it differs from the reference's sequential f64 accumulation only in rounding order.
 // Algorithmic bytes: COUNT 32 B/segment, MIN 4, MAX 4, SUM/AVG 73 B/segment + payloads.
+#include "mdb_agg_dev.hpp"
 #include "mdb_segment_dev.hpp"
 
 #include <cfloat>
@@ -240,160 +241,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_finish(const AggPartial *__
 }
 
 // ---- time-range extension ---------------------------------------------------------------------------
-
-struct RangeAcc {
-    double sum = 0.0;
-    long long count = 0;
-    float min = FLT_MAX;
-    float max = -FLT_MAX;
-    __device__ __forceinline__ void point(float v) {
-        sum += (double)v;
-        count += 1;
-        min = min_num(min, v);
-        max = max_num(max, v);
-    }
-};
-
-__device__ __forceinline__ float model_value_at(const SegDesc &d, uint32_t type, int64_t t) {
-    return type == MDB_PMC_MEAN_ID ? d.value : (float)(d.slope * (double)t + d.intercept);
-}
-
-// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi].
-// tail_by_pieces: the residual tail's points are k_agg_mv_range's (regular timestamps only).
-__device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, const SegInfo &info,
-                                              int64_t t_lo, int64_t t_hi, RangeAcc &acc,
-                                              uint32_t *error, bool tail_by_pieces = false) {
-    const SegDesc &d = info.desc;
-    const uint32_t type = d.flags & FLAG_TYPE_MASK;
-    const int64_t end = s.end_time[i];
-    const uint32_t n_res = d.n_total - d.n_model;
-    if (!(d.flags & FLAG_REGULAR)) {
-        // Irregular timestamps: one serial pass, every point tested.
-        if (end < t_lo || d.start > t_hi) return;
-        const uint4 vt = s.timestamps.views[i];
-        const uint8_t *ts_bytes = view_data(s.timestamps, i, vt);
-        if (type != MDB_MACAQUE_V_ID && n_res == 0) {
-            decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error,
-                                        [&](uint32_t, int64_t t) {
-                                            if (t >= t_lo && t <= t_hi)
-                                                acc.point(model_value_at(d, type, t));
-                                        });
-            return;
-        }
-        // Values are a bitstream too (MacaqueV model or residual tail): first find the index
-        // interval of the in-range timestamps, then decode the values once. Rare combination.
-        uint32_t k_lo = 0xffffffffu, k_hi = 0;
-        decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error,
-                                    [&](uint32_t k, int64_t t) {
-                                        if (t >= t_lo && t <= t_hi) {
-                                            if (k < k_lo) k_lo = k;
-                                            if (k > k_hi) k_hi = k;
-                                        }
-                                    });
-        if (k_lo == 0xffffffffu) return;
-        // Timestamps are sorted, so the in-range points are exactly the indices k_lo..k_hi.
-        float seed = d.value;
-        if (type == MDB_MACAQUE_V_ID) {
-            const uint4 vv = s.values.views[i];
-            uint32_t last_bits = 0;
-            decode_macaque_v(view_data(s.values, i, vv), vv.x, d.n_model, false, 0, error,
-                             [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) acc.point(__uint_as_float(bits));
-                                 last_bits = bits;
-                             });
-            seed = __uint_as_float(last_bits);
-        } else {
-            decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, d.n_model, error,
-                                        [&](uint32_t k, int64_t t) {
-                                            if (k >= k_lo && k <= k_hi)
-                                                acc.point(model_value_at(d, type, t));
-                                        });
-        }
-        if (n_res > 0) {
-            const uint4 vr = s.residuals.views[i];
-            decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, n_res, true,
-                             __float_as_uint(seed), error, [&](uint32_t k, uint32_t bits) {
-                                 uint32_t index = d.n_model + k;
-                                 if (index >= k_lo && index <= k_hi) acc.point(__uint_as_float(bits));
-                             });
-        }
-        return;
-    }
-
-    // Regular timestamps start + k * delta: the in-range indices are an interval [k_lo, k_hi].
-    uint32_t k_lo = 0, k_hi = 0;
-    if (!regular_index_interval(d.start, d.delta, d.n_total, t_lo, t_hi, &k_lo, &k_hi)) return;
-
-    // Model part [a, b] of the interval.
-    if (type != MDB_MACAQUE_V_ID && k_lo < d.n_model) {
-        const uint32_t a = k_lo;
-        const uint32_t b = min(k_hi, d.n_model - 1);
-        const uint32_t n = b - a + 1;
-        const int64_t ta = d.start + (int64_t)((uint64_t)a * (uint64_t)d.delta);
-        const int64_t tb = d.start + (int64_t)((uint64_t)b * (uint64_t)d.delta);
-        const float va = model_value_at(d, type, ta);
-        const float vb = model_value_at(d, type, tb);
-        // (float)(slope * t + intercept) is monotone in t, so the extremes sit at the ends.
-        acc.min = min_num(acc.min, min_num(va, vb));
-        acc.max = max_num(acc.max, max_num(va, vb));
-        acc.count += n;
-        if (type == MDB_PMC_MEAN_ID) {
-            acc.sum += (double)d.value * (double)n;
-        } else {
-            // Sum of the line over n equally spaced points: the f64 closed form of the f32 values
-            // grid() would produce - unless it could miss their sum by more than a tenth of the
-            // 0.001 % the reference allows (integration_test.rs:1155-1171). That happens when
-            // slope * t + intercept cancels almost completely (epoch timestamps, a model that lasts
-            // microseconds, values near zero): every reconstructed point then carries rounding noise
-            // of ulp(slope * t), which averages out over the points but not over the two end points
-            // the closed form uses. The bound below is the worst case of that noise plus the f32
-            // rounding of the points; beyond it the points are summed one by one, which is exactly
-            // what the reference's plan (GridExec + filter + SUM) computes.
-            const double fa = d.slope * (double)ta + d.intercept;
-            const double fb = d.slope * (double)tb + d.intercept;
-            const double closed = (fa + fb) / 2.0 * (double)n;
-            const double magnitude = fmax(fabs(fa), fabs(fb));
-            const double cancelled = fmax(fmax(fabs(d.slope * (double)ta), fabs(d.slope * (double)tb)),
-                                          fabs(d.intercept));
-            const double worst = (double)n * (6.0e-8 * magnitude + 7.0e-46 + 2.3e-16 * cancelled);
-            if (worst <= 1.0e-6 * fabs(closed)) {
-                acc.sum += closed;
-            } else {
-                double pointwise = 0.0;
-                for (uint32_t k = a; k <= b; k++) {
-                    const int64_t t = d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta);
-                    pointwise += (double)model_value_at(d, type, t);
-                }
-                acc.sum += pointwise;
-            }
-        }
-    }
-    float seed = d.value;
-    if (type == MDB_MACAQUE_V_ID) {
-        const uint4 vv = s.values.views[i];
-        uint32_t last_bits = 0;
-        // Decode only as far as needed unless the residual seed (last value) is needed too.
-        const bool residuals_in_range = n_res > 0 && k_hi >= d.n_model;
-        const uint32_t upto = residuals_in_range ? d.n_model : min(d.n_model, k_hi + 1);
-        if (k_lo < d.n_model || residuals_in_range) {
-            decode_macaque_v(view_data(s.values, i, vv), vv.x, upto, false, 0, error,
-                             [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) acc.point(__uint_as_float(bits));
-                                 last_bits = bits;
-                             });
-        }
-        seed = __uint_as_float(last_bits);
-    }
-    if (n_res > 0 && k_hi >= d.n_model && !tail_by_pieces) {
-        const uint4 vr = s.residuals.views[i];
-        const uint32_t upto = k_hi - d.n_model + 1;
-        decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, upto, true, __float_as_uint(seed),
-                         error, [&](uint32_t k, uint32_t bits) {
-                             uint32_t index = d.n_model + k;
-                             if (index >= k_lo) acc.point(__uint_as_float(bits));
-                         });
-    }
-}
+// (RangeAcc and segment_range, the points of one segment inside the range: mdb_agg_dev.hpp)
 
 // `walked_totals`, `walked_ranges`, `walked_error` (all may be nullptr): of the segments with irregular timestamps
 // that reach into the range, len() and - PMC-Mean / Swing without residuals - the aggregates of their points inside

@@ -1,0 +1,536 @@
+// mdb_buckets.hip - COUNT / MIN / MAX / SUM per date_bin bucket and group, computed on segments.
+//
+// What the reference answers for SELECT <tags>, date_bin(width, ts, origin), AGG(field) ... GROUP BY 1, 2 with
+// GridExec + the date_bin / range filter + AggregateExec (its model-based rule only takes an empty GROUP BY,
+// crates/modelardb_storage/src/optimizer/model_simple_aggregates.rs:219), without materialising a point. The range
+// aggregate (mdb_agg.hip, k_agg_range) is the one-bucket case: every (segment, bucket) pair below is one call of its
+// segment_range, or - for segments whose points live in a bit stream - one stretch of a single decode.
+//
+//   k_agg_bucket_span      1 lane / segment: how many buckets the segment reaches (from start_time / end_time alone,
+//                          clipped by [t_lo, t_hi] and buckets 0 .. n_buckets-1), and its group id checked. A scan
+//                          (mdb_scan.hpp) makes pair offsets; one read-back sizes the work.
+//   then per slice of at most MDB_AGG_BUCKET_SLICE_PAIRS pairs (bounded scratch), slices folded in order:
+//   k_agg_bucket_partials  1 lane / segment with pairs in the slice: {f64 sum, count, min, max} and the cell key
+//                          group * n_buckets + b of each of its pairs. PMC-Mean / Swing on regular timestamps: O(1)
+//                          per pair (segment_range's closed forms, its tail decode for residuals). MacaqueV values or
+//                          irregular timestamps: the stream is decoded once, a partial flushed at each bucket edge -
+//                          unless the stream is in the batch's cursor index (regular timestamps: MacaqueV values, the
+//                          residual tails of PMC-Mean / Swing): then k_agg_bucket_pieces (mdb_grid.hip) decodes it one
+//                          lane per piece of 64 values and writes one entry {key, partial} per bucket a piece reaches;
+//                          the entries are reduced and folded like the pairs, in slices behind them.
+//   k_agg_bucket_check     are the keys non-decreasing in pair order (ModelarDB's storage order: segments by tags, then
+//                          start_time, groups following the tags)? If not, a stable radix sort by key (rocPRIM).
+//   k_agg_bucket_tree      runs of equal keys reduced through a fixed tree of 64-entry tiles: level l+1 holds, per
+//                          tile of level l, its last key and the fold of the run that ends the tile.
+//   k_agg_bucket_fold      1 lane / pair: the lane of a run's last pair folds the run (its tile, then one tile's
+//                          entry per level up) and merges it into the cell - no two lanes write one cell, no float
+//                          atomics, the order of every addition fixed by the pair order: run-to-run deterministic.
+// Bytes (Swing on regular timestamps): ~70 B of metadata per segment read, 32 B per pair written and read back.
+#include "mdb_agg_dev.hpp"
+#include "mdb_scan.hpp"
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cstdlib>
+#include <vector>
+
+namespace mdb {
+
+constexpr int BUCKET_THREADS = 256;
+constexpr uint32_t BUCKET_TILE = 64;                    // entries per lane and level of the reduction tree
+constexpr int BUCKET_MAX_LEVELS = 12;                   // 64^11 > 2^64
+constexpr uint64_t BUCKET_SLICE_DEFAULT = 1ull << 24;   // pairs per slice: 512 MB of partials and keys
+constexpr uint64_t BUCKET_SLICE_MAX = 1ull << 31;       // (pair numbers of the sort path are 32-bit)
+constexpr uint32_t ERR_BUCKET_GROUP = 1u << 31;         // k_agg_bucket_span: a group id >= n_groups
+
+struct BucketTree { // level 0 is the slice's pairs (keys, partials, and the sort's pair numbers); 1.. are the tree's
+    const unsigned long long *keys[BUCKET_MAX_LEVELS];
+    const BucketPartial *values[BUCKET_MAX_LEVELS];
+    uint64_t n[BUCKET_MAX_LEVELS];
+    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
+    int levels;
+};
+
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_span(DevSegments s, const uint32_t *__restrict__ groups,
+                                                                    BucketRequest r,
+                                                                    unsigned long long *__restrict__ counts,
+                                                                    unsigned int *__restrict__ error) {
+    const uint64_t i = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
+    if (i >= s.n) return;
+    uint64_t first = 0;
+    uint64_t count = bucket_span(s.start_time[i], s.end_time[i], r, &first);
+    if (groups && groups[i] >= r.n_groups) {
+        atomicOr(error, ERR_BUCKET_GROUP);
+        count = 0;
+    }
+    counts[i] = count;
+}
+
+struct BucketCountOf {
+    const unsigned long long *counts;
+    __device__ uint64_t operator()(uint64_t i) const { return counts[i]; }
+};
+
+// The pairs of a segment whose points are a bit stream (MacaqueV values, irregular timestamps): slots [j0, j1) of the
+// slice, buckets b_first + (j - off). Pass 1 leaves each slot's index interval [k_lo, k_hi] of points in its sum
+// field (k_lo > k_hi: no point); pass 2 decodes the values once, each into the slot whose interval holds it, and
+// overwrites every slot with its partial. Returns false when the timestamps turn out not to be sorted (a malformed
+// stream): the caller then overwrites the slots with segment_range pair by pair, which tests every point.
+__device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const SegInfo &info, const BucketRequest &r,
+                                       uint64_t off, uint64_t b_first, uint64_t j0, uint64_t j1, uint64_t p0,
+                                       BucketPartial *__restrict__ out, uint32_t *error) {
+    const SegDesc &d = info.desc;
+    const uint32_t type = d.flags & FLAG_TYPE_MASK;
+    const int64_t end = s.end_time[i];
+    const uint32_t n_res = d.n_total - d.n_model;
+    auto interval = [&](uint64_t j) -> uint2 * { return reinterpret_cast<uint2 *>(&out[j - p0].sum); };
+    uint32_t needed = 0; // points [0, needed) reach a slot
+    if (d.flags & FLAG_REGULAR) {
+        for (uint64_t j = j0; j < j1; j++) {
+            int64_t lo, hi;
+            bucket_bounds(r, b_first + (j - off), &lo, &hi);
+            uint32_t k_lo = 1, k_hi = 0;
+            if (regular_index_interval(d.start, d.delta, d.n_total, lo, hi, &k_lo, &k_hi)) needed = k_hi + 1;
+            else k_lo = 1, k_hi = 0;
+            *interval(j) = make_uint2(k_lo, k_hi);
+        }
+    } else {
+        for (uint64_t j = j0; j < j1; j++) *interval(j) = make_uint2(1, 0);
+        const uint4 vt = s.timestamps.views[i];
+        uint64_t slot = ~0ull;
+        uint32_t k_lo = 0, k_hi = 0;
+        int64_t previous = INT64_MIN;
+        bool sorted = true;
+        decode_irregular_timestamps(view_data(s.timestamps, i, vt), vt.x, d.start, end, 0xffffffffu, error,
+                                    [&](uint32_t k, int64_t t) {
+                                        if (t < previous) sorted = false;
+                                        previous = t;
+                                        if (!sorted || t < r.t_lo || t > r.t_hi || t < r.origin) return;
+                                        const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
+                                        if (b < b_first || b >= r.n_buckets) return;
+                                        const uint64_t j = off + (b - b_first);
+                                        if (j < j0 || j >= j1) return;
+                                        if (j != slot) {
+                                            if (slot != ~0ull) *interval(slot) = make_uint2(k_lo, k_hi);
+                                            slot = j;
+                                            k_lo = k;
+                                        }
+                                        k_hi = k;
+                                    });
+        if (!sorted) return false;
+        if (slot != ~0ull) {
+            *interval(slot) = make_uint2(k_lo, k_hi);
+            needed = k_hi + 1;
+        }
+    }
+
+    // Pass 2: the points in index order; slot j's interval is read before its partial overwrites it.
+    uint64_t j = j0;
+    uint2 current = *interval(j);
+    RangeAcc acc;
+    auto flush = [&]() {
+        out[j - p0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
+        acc = RangeAcc();
+        j++;
+        if (j < j1) current = *interval(j);
+    };
+    auto visit = [&](uint32_t k, float v) {
+        while (j < j1 && k > current.y) flush();
+        if (j < j1 && k >= current.x) acc.point(v);
+    };
+    if (needed > 0) {
+        float seed = d.value;
+        if (type == MDB_MACAQUE_V_ID) {
+            const uint4 vv = s.values.views[i];
+            uint32_t last_bits = 0;
+            const bool residuals_needed = n_res > 0 && needed > d.n_model;
+            decode_macaque_v(view_data(s.values, i, vv), vv.x, residuals_needed ? d.n_model : min(d.n_model, needed),
+                             false, 0, error, [&](uint32_t k, uint32_t bits) {
+                                 visit(k, __uint_as_float(bits));
+                                 last_bits = bits;
+                             });
+            seed = __uint_as_float(last_bits);
+        } else if (d.n_model > 0) { // PMC-Mean / Swing on irregular timestamps: the model at each timestamp
+            const uint4 vt = s.timestamps.views[i];
+            decode_irregular_timestamps(view_data(s.timestamps, i, vt), vt.x, d.start, end, min(d.n_model, needed), error,
+                                        [&](uint32_t k, int64_t t) {
+                                            if (k < d.n_model) visit(k, model_value_at(d, type, t));
+                                        });
+        }
+        if (n_res > 0 && needed > d.n_model) {
+            const uint4 vr = s.residuals.views[i];
+            decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, needed - d.n_model, true, __float_as_uint(seed),
+                             error, [&](uint32_t k, uint32_t bits) { visit(d.n_model + k, __uint_as_float(bits)); });
+        }
+    }
+    while (j < j1) flush();
+    return true;
+}
+
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegments s,
+                                                                        const uint32_t *__restrict__ groups,
+                                                                        BucketRequest r,
+                                                                        const unsigned long long *__restrict__ offsets,
+                                                                        uint64_t p0, uint64_t p1,
+                                                                        BucketPartial *__restrict__ out,
+                                                                        unsigned long long *__restrict__ keys,
+                                                                        unsigned int *__restrict__ error_out,
+                                                                        const unsigned long long *__restrict__ piece_base) {
+    const uint64_t i = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
+    if (i >= s.n) return;
+    const uint64_t off = offsets[i], stop = offsets[i + 1];
+    const uint64_t j0 = off > p0 ? off : p0, j1 = stop < p1 ? stop : p1;
+    if (j0 >= j1) return;
+    uint64_t b_first = 0;
+    (void)bucket_span(s.start_time[i], s.end_time[i], r, &b_first);
+    const uint64_t row = (uint64_t)(groups ? groups[i] : 0u) * r.n_buckets;
+    for (uint64_t j = j0; j < j1; j++) keys[j - p0] = row + b_first + (j - off);
+    SegInfo info = analyse_segment(s, i);
+    uint32_t error = info.error;
+    if (!error && bucket_values_by_pieces(s, i, info, piece_base)) {
+        // (every point is k_agg_bucket_pieces': the pairs stay empty)
+        for (uint64_t j = j0; j < j1; j++) out[j - p0] = bucket_empty();
+    } else if (!error) {
+        const bool tail_by_pieces = bucket_tail_by_pieces(s, i, info, piece_base); // (the model's points only, then)
+        const bool stream = !(info.desc.flags & FLAG_REGULAR) || (info.desc.flags & FLAG_TYPE_MASK) == MDB_MACAQUE_V_ID;
+        if (!stream || !bucket_stream_partials(s, i, info, r, off, b_first, j0, j1, p0, out, &error)) {
+            for (uint64_t j = j0; j < j1; j++) {
+                int64_t lo, hi;
+                bucket_bounds(r, b_first + (j - off), &lo, &hi);
+                RangeAcc acc;
+                segment_range(s, i, info, lo, hi, acc, &error, tail_by_pieces);
+                out[j - p0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
+            }
+        }
+    }
+    if (error) atomicOr(error_out, error);
+}
+
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_check(const unsigned long long *__restrict__ keys,
+                                                                     uint64_t n, unsigned int *__restrict__ unsorted) {
+    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x + 1;
+    if (j < n && keys[j] < keys[j - 1]) atomicOr(unsorted, 1u);
+}
+
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_iota(uint32_t *__restrict__ out, uint64_t n) {
+    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
+    if (j < n) out[j] = (uint32_t)j;
+}
+
+__device__ __forceinline__ BucketPartial bucket_value(const BucketTree &tree, int level, uint64_t t) {
+    return tree.values[level][level == 0 && tree.order ? tree.order[t] : t];
+}
+
+// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the fold of the run ending it.
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_tree(BucketTree tree, int level,
+                                                                    unsigned long long *__restrict__ keys_out,
+                                                                    BucketPartial *__restrict__ values_out) {
+    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
+    const uint64_t n = tree.n[level];
+    const uint64_t first = u * BUCKET_TILE;
+    if (first >= n) return;
+    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
+    const unsigned long long *keys = tree.keys[level];
+    const unsigned long long key = keys[last];
+    BucketPartial acc = bucket_value(tree, level, last);
+    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) bucket_add(acc, bucket_value(tree, level, t - 1));
+    keys_out[u] = key;
+    values_out[u] = acc;
+}
+
+// The lane of the last pair of each run of equal keys folds the run and merges it into its cell (mdb_agg_merge's
+// rules, for the aggregates in which_mask); a run without points leaves the cell alone.
+__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_fold(BucketTree tree, uint32_t which_mask,
+                                                                    mdb_agg_state *__restrict__ cells) {
+    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
+    const uint64_t n = tree.n[0];
+    if (j >= n) return;
+    const unsigned long long key = tree.keys[0][j];
+    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
+    BucketPartial acc = bucket_empty();
+    uint64_t index = j;
+    for (int level = 0; level < tree.levels; level++) {
+        const uint64_t first = index - index % BUCKET_TILE;
+        const unsigned long long *keys = tree.keys[level];
+        uint64_t t = index;
+        bool whole = true; // every entry from `first` to `index` belongs to the run
+        while (true) {
+            if (keys[t] != key) {
+                whole = false;
+                break;
+            }
+            bucket_add(acc, bucket_value(tree, level, t));
+            if (t == first) break;
+            t--;
+        }
+        if (!whole || first == 0) break;
+        index = first / BUCKET_TILE - 1; // the tile in front, one level up
+    }
+    if (acc.count == 0) return;
+    mdb_agg_state cell = cells[key];
+    if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) cell.count += acc.count;
+    if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) cell.sum += acc.sum;
+    if ((which_mask & MDB_AGG_MIN) && !(acc.min != acc.min) && (cell.min != cell.min || acc.min < cell.min))
+        cell.min = acc.min;
+    if ((which_mask & MDB_AGG_MAX) && !(acc.max != acc.max) && (cell.max != cell.max || acc.max > cell.max))
+        cell.max = acc.max;
+    cells[key] = cell;
+}
+
+static uint64_t align_256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
+
+static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + BUCKET_THREADS - 1) / BUCKET_THREADS); }
+
+static uint64_t slice_pairs_setting() {
+    if (const char *text = option_text("MDB_AGG_BUCKET_SLICE_PAIRS")) {
+        const long long value = std::atoll(text);
+        if (value >= 1) return std::min<uint64_t>((uint64_t)value, BUCKET_SLICE_MAX);
+    }
+    return BUCKET_SLICE_DEFAULT;
+}
+
+// The host-side checks every form makes before it touches the device.
+static int bucket_request_check(const mdb_bucket_request *request, uint64_t *n_cells) {
+    if (request->width <= 0) return fail("The bucket width must be positive.");
+    if (request->n_groups == 0) return fail("n_groups must be at least 1.");
+    const unsigned __int128 cells = (unsigned __int128)request->n_groups * request->n_buckets;
+    if (cells * sizeof(mdb_agg_state) > (unsigned __int128)UINT64_MAX)
+        return fail("n_groups * n_buckets overflows.");
+    *n_cells = (uint64_t)cells;
+    return 0;
+}
+
+// The buckets of the device batch `in` (groups: a device array or nullptr) folded into `cells_target`, a device array
+// of n_cells states. `host_cells` (host forms): the caller's array, which is uploaded, folded and downloaded instead;
+// either way nothing of the caller's is written unless the whole call succeeds.
+int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, const mdb_bucket_request *request,
+                uint64_t n_cells, mdb_agg_state *dev_cells, mdb_agg_state *host_cells) {
+    const uint64_t n = in->n;
+    if (n == 0 || request->n_buckets == 0) return 0;
+    const BucketRequest r = {request->origin, request->width, request->n_buckets, request->t_lo, request->t_hi,
+                             request->n_groups, request->which_mask};
+    if (n > UINT64_MAX / request->n_buckets)
+        return fail("Too many (segment, bucket) pairs for one call: split the batch.");
+    const DevSegments s = to_dev(in);
+
+    // Span: pair offsets and the read-back words (total pairs, error, unsorted).
+    void *p;
+    const uint64_t offsets_bytes = align_256((n + 1) * 8), sums_bytes = align_256(scan_block_sums_bytes(n));
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_SPAN, 2 * offsets_bytes + sums_bytes + 256, &p)) return 1;
+    unsigned long long *counts = static_cast<unsigned long long *>(p);
+    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + offsets_bytes);
+    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + 2 * offsets_bytes);
+    unsigned int *words = reinterpret_cast<unsigned int *>(static_cast<char *>(p) + 2 * offsets_bytes + sums_bytes);
+    MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
+    {
+        LaunchTimer timer(ctx, "k_agg_bucket_span");
+        hipLaunchKernelGGL(k_agg_bucket_span, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, r,
+                           counts, words);
+    }
+    if (device_exclusive_scan(ctx, BucketCountOf{counts}, n, offsets, block_sums, "k_agg_bucket_scan")) return 1;
+    unsigned long long total = 0;
+    unsigned int span_error = 0;
+    MDB_HIP_CHECK(hipMemcpyAsync(&total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipMemcpyAsync(&span_error, words, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    if (span_error & ERR_BUCKET_GROUP) return fail("A group id is not below n_groups.");
+    if (total == 0) return 0;
+    // The MacaqueV streams of the batch's cursor index (built here for a batch the library holds; MDB_GRID_MV_INDEX=0:
+    // none) go piece by piece: their entries are folded behind the pairs, in slices of their own.
+    std::shared_ptr<MvIndex> index;
+    const unsigned long long *piece_base = nullptr, *entry_offsets = nullptr;
+    unsigned long long entries = 0;
+    if (mv_index_for_range(ctx, in, &index, &piece_base)) return 1;
+    if (piece_base && bucket_pieces_count(ctx, s, r, piece_base, *index, &entry_offsets, &entries)) return 1;
+
+    const uint64_t slice = slice_pairs_setting();
+    const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
+    const uint64_t n_slices = pair_slices + entry_slices;
+    const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
+    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
+    // a working copy otherwise.
+    mdb_agg_state *cells = dev_cells;
+    if (host_cells || n_slices > 1) {
+        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_agg_state), &p)) return 1;
+        cells = static_cast<mdb_agg_state *>(p);
+        if (host_cells)
+            MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells, n_cells * sizeof(mdb_agg_state), hipMemcpyHostToDevice,
+                                         ctx->stream));
+        else
+            MDB_HIP_CHECK(hipMemcpyAsync(cells, dev_cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToDevice,
+                                         ctx->stream));
+    }
+    const uint64_t partials_bytes = align_256(cap * sizeof(BucketPartial));
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, partials_bytes + cap * 8, &p)) return 1;
+    BucketPartial *partials = static_cast<BucketPartial *>(p);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + partials_bytes);
+    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries.
+    uint64_t tree_entries = 0;
+    for (uint64_t m = cap; m > BUCKET_TILE;) {
+        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
+        tree_entries += m + 1;
+    }
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(BucketPartial)) + 256, &p)) return 1;
+    unsigned long long *tree_keys = static_cast<unsigned long long *>(p);
+    BucketPartial *tree_values = reinterpret_cast<BucketPartial *>(tree_keys + tree_entries);
+    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
+    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+
+    for (uint64_t k = 0; k < n_slices; k++) {
+        // (slices of pairs first, then slices of the pieces' entries)
+        const bool pairs = k < pair_slices;
+        const uint64_t p0 = (pairs ? k : k - pair_slices) * slice;
+        const uint64_t p1 = std::min<uint64_t>(p0 + slice, pairs ? total : entries), m = p1 - p0;
+        MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
+        if (pairs) {
+            LaunchTimer timer(ctx, "k_agg_bucket_partials");
+            hipLaunchKernelGGL(k_agg_bucket_partials, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s,
+                               groups, r, offsets, p0, p1, partials, keys, words, piece_base);
+        } else if (bucket_pieces_entries(ctx, s, r, groups, piece_base, *index, entry_offsets, p0, p1, keys, partials)) {
+            return 1;
+        }
+        if (m > 1) {
+            LaunchTimer timer(ctx, "k_agg_bucket_check");
+            hipLaunchKernelGGL(k_agg_bucket_check, dim3(blocks_for(m - 1)), dim3(BUCKET_THREADS), 0, ctx->stream, keys,
+                               m, words + 1);
+        }
+        unsigned int read_back[2] = {0, 0};
+        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
+        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        MDB_HIP_CHECK(hipGetLastError());
+        if (read_back[0]) return fail(describe_error(read_back[0]));
+
+        BucketTree tree = {};
+        tree.keys[0] = keys;
+        tree.values[0] = partials;
+        tree.n[0] = m;
+        tree.order = nullptr;
+        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
+            const uint64_t keys_bytes = align_256(m * 8), order_bytes = align_256(m * 4);
+            size_t sort_bytes = 0;
+            MDB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys, static_cast<uint32_t *>(nullptr),
+                                                    static_cast<uint32_t *>(nullptr), (size_t)m, 0u, key_bits,
+                                                    ctx->stream));
+            if (scratch_reserve(ctx, SCRATCH_BUCKET_SORT, keys_bytes + 2 * order_bytes + sort_bytes, &p)) return 1;
+            unsigned long long *sorted_keys = static_cast<unsigned long long *>(p);
+            uint32_t *order_in = reinterpret_cast<uint32_t *>(static_cast<char *>(p) + keys_bytes);
+            uint32_t *order = reinterpret_cast<uint32_t *>(static_cast<char *>(p) + keys_bytes + order_bytes);
+            void *sort_storage = static_cast<char *>(p) + keys_bytes + 2 * order_bytes;
+            LaunchTimer timer(ctx, "k_agg_bucket_sort");
+            hipLaunchKernelGGL(k_agg_bucket_iota, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, order_in, m);
+            MDB_HIP_CHECK(rocprim::radix_sort_pairs(sort_storage, sort_bytes, keys, sorted_keys, order_in, order,
+                                                    (size_t)m, 0u, key_bits, ctx->stream));
+            tree.keys[0] = sorted_keys;
+            tree.order = order;
+        }
+        // The tree's levels over this slice, then the fold.
+        tree.levels = 1;
+        uint64_t used = 0;
+        {
+            LaunchTimer timer(ctx, "k_agg_bucket_tree");
+            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
+                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
+                unsigned long long *level_keys = tree_keys + used;
+                BucketPartial *level_values = tree_values + used;
+                hipLaunchKernelGGL(k_agg_bucket_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
+                                   tree.levels - 1, level_keys, level_values);
+                tree.keys[tree.levels] = level_keys;
+                tree.values[tree.levels] = level_values;
+                tree.n[tree.levels] = up;
+                used += up + 1;
+                size = up;
+            }
+        }
+        {
+            LaunchTimer timer(ctx, "k_agg_bucket_fold");
+            hipLaunchKernelGGL(k_agg_bucket_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
+                               r.which_mask, cells);
+        }
+    }
+    // (every slice has been found free of errors: the caller's cells are written now, and only now)
+    if (host_cells)
+        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToHost,
+                                     ctx->stream));
+    else if (cells != dev_cells)
+        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToDevice,
+                                     ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The group ids of the host forms, uploaded next to the batch (nullptr: every segment in group 0).
+static int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs,
+                         uint64_t n, const uint32_t **out) {
+    *out = nullptr;
+    bool any = false;
+    for (uint32_t k = 0; k < n_inputs; k++) any = any || (groups && groups[k] && rows[k] > 0);
+    if (!any || n == 0) return 0;
+    void *p;
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_GROUPS, n * 4, &p)) return 1;
+    uint32_t *dev = static_cast<uint32_t *>(p);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n_inputs; k++) {
+        if (groups[k])
+            MDB_HIP_CHECK(hipMemcpyAsync(dev + at, groups[k], rows[k] * 4, hipMemcpyHostToDevice, ctx->stream));
+        else
+            MDB_HIP_CHECK(hipMemsetAsync(dev + at, 0, rows[k] * 4, ctx->stream));
+        at += rows[k];
+    }
+    *out = dev;
+    return 0;
+}
+
+} // namespace mdb
+
+using namespace mdb;
+
+extern "C" {
+
+int mdb_agg_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                        const mdb_bucket_request *request, mdb_agg_state *inout) {
+    if (!ctx || !in || !request || !inout) return fail("ctx, in, request and inout must not be NULL.");
+    uint64_t n_cells = 0;
+    if (bucket_request_check(request, &n_cells)) return 1;
+    mdb::CallGuard lock(ctx);
+    MDB_HIP_CHECK(hipSetDevice(ctx->device));
+    return buckets_run(ctx, in, group_of_segment, request, n_cells, inout, nullptr);
+}
+
+int mdb_agg_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                         uint32_t n_inputs, const mdb_bucket_request *request, mdb_agg_state *inout) {
+    if (!ctx || !inputs || !request || !inout) return fail("ctx, inputs, request and inout must not be NULL.");
+    uint64_t n_cells = 0;
+    if (bucket_request_check(request, &n_cells)) return 1;
+    std::vector<uint64_t> rows(n_inputs);
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < n_inputs; k++) {
+        if (!inputs[k]) return fail("A batch of the list is NULL.");
+        rows[k] = inputs[k]->n;
+        n += rows[k];
+    }
+    if (n == 0 || request->n_buckets == 0) return 0;
+    mdb::CallGuard lock(ctx);
+    MDB_HIP_CHECK(hipSetDevice(ctx->device));
+    // (an upload the library holds, not its transient scratch: the batch then gets the cursor index a resident batch
+    // gets, and the host and device forms decode the same streams the same way - bit-identical results)
+    mdb_segments_owned *dev = nullptr;
+    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
+    const uint32_t *groups = nullptr;
+    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
+    if (!rc) rc = buckets_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
+    mdb_segments_free(dev);
+    return rc;
+}
+
+int mdb_agg_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                    const mdb_bucket_request *request, mdb_agg_state *inout) {
+    if (!in) return fail("in must not be NULL.");
+    const uint32_t *const groups[1] = {group_of_segment};
+    return mdb_agg_buckets_list(ctx, &in, groups, 1, request, inout);
+}
+
+} // extern "C"

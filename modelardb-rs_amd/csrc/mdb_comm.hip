@@ -189,4 +189,11 @@ int mdb_agg_merge(mdb_agg_state *into, const mdb_agg_state *from) {
     return 0;
 }
 
+int mdb_agg_merge_n(mdb_agg_state *into, const mdb_agg_state *from, uint64_t n) {
+    if (n == 0) return 0;
+    if (!into || !from) return fail("into and from must not be NULL.");
+    for (uint64_t k = 0; k < n; k++) merge_agg_state(into + k, from[k]);
+    return 0;
+}
+
 } // extern "C"

@@ -82,6 +82,13 @@ enum ScratchSlot {
     SCRATCH_FIT_ROTATION,
     SCRATCH_FIT_GAP_STAGE_OFFSETS,
     SCRATCH_FIT_GAP_STAGE,
+    SCRATCH_BUCKET_SPAN,  // mdb_agg_buckets: pair offsets per segment, scan block sums, the read-back words
+    SCRATCH_BUCKET_PAIRS, // ... one slice's (segment, bucket) partials and keys
+    SCRATCH_BUCKET_SORT,  // ... the sort path: keys and pair numbers in key order, the radix sort's storage
+    SCRATCH_BUCKET_TREE,  // ... the upper levels of the reduction
+    SCRATCH_BUCKET_CELLS, // ... the working copy of the caller's cells (host forms, several slices)
+    SCRATCH_BUCKET_GROUPS, // ... the group ids of the host forms
+    SCRATCH_BUCKET_PIECES, // ... entry counts and offsets of the MacaqueV pieces (mdb_grid.hip)
     SCRATCH_SLOT_COUNT
 };
 

@@ -26,6 +26,7 @@
 //                    value streams, residual tails (<= 255 values) and the few irregular timestamp
 //                    streams short enough to live inside their view overwrite the placeholders.
 // Algorithmic bytes: 73 B/segment read + 12 B/point written (8 B timestamp + 4 B value).
+#include "mdb_agg_dev.hpp"
 #include "mdb_segment_dev.hpp"
 #include "mdb_scan.hpp"
 #include "mdb_macaque_parallel.hpp"
@@ -4149,6 +4150,180 @@ __global__ __launch_bounds__(MDB_WAVE) void k_agg_mv_range(DevSegments s, TimeRa
 #pragma unroll
     for (int delta = MDB_WAVE / 2; delta > 0; delta >>= 1) mine.merge(shfl_down_partial(mine, delta));
     if (lane == 0) partials[blockIdx.x] = mine;
+}
+
+// ---- date_bin buckets over the pieces of MacaqueV streams (mdb_buckets.hip) ------------------------------------
+// The streams bucket_values_by_pieces / bucket_tail_by_pieces take (regular timestamps: point k at start + k delta)
+// are aggregated like k_agg_mv_range does under a time range - one lane per piece of 64 values, every lane decoding
+// in every step - but each lane flushes a partial at every bucket edge: ENTRIES {key, partial}, one per bucket its
+// visible values reach (empty ones included), at offsets a count per piece and a scan have given. Entries of one
+// stream follow each other in key order; mdb_buckets.hip reduces and folds them like its (segment, bucket) pairs.
+
+// The visible values [from, upto) of the piece (segment-level indices) and the buckets [b_first, b_last] they reach;
+// false: the piece is not taken or holds no visible value.
+__device__ __forceinline__ bool bucket_piece_span(const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
+                                                  const uint4 &c0, const uint4 &c1, SegInfo *info_out, uint32_t *from,
+                                                  uint32_t *upto, uint64_t *b_first, uint64_t *b_last) {
+    const uint32_t i = c0.z, point_index = c0.w, n_values = c1.x, window = c1.y;
+    const uint4 ts_view = s.timestamps.views[i];
+    if ((int32_t)ts_view.x > 0 && (view_inline_byte(ts_view, 0) & 0x80u) != 0) return false; // (irregular: not taken)
+    uint64_t unused = 0;
+    if (bucket_span(s.start_time[i], s.end_time[i], r, &unused) == 0) return false;
+    const SegInfo info = analyse_segment(s, i);
+    const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
+    if (!(residual ? bucket_tail_by_pieces(s, i, info, piece_base) : bucket_values_by_pieces(s, i, info, piece_base)))
+        return false;
+    const int64_t lo = r.t_lo > r.origin ? r.t_lo : r.origin;
+    const int64_t last = buckets_last_time(r);
+    const int64_t hi = r.t_hi < last ? r.t_hi : last;
+    uint32_t k_lo = 0, k_hi = 0;
+    if (lo > hi || !regular_index_interval(info.desc.start, info.desc.delta, info.desc.n_total, lo, hi, &k_lo, &k_hi))
+        return false;
+    *from = max(k_lo, point_index);
+    *upto = min(k_hi + 1, point_index + n_values);
+    if (*from >= *upto) return false;
+    const SegDesc &d = info.desc;
+    const uint64_t width = (uint64_t)r.width;
+    *b_first = ((uint64_t)(d.start + (int64_t)((uint64_t)*from * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
+    *b_last = ((uint64_t)(d.start + (int64_t)((uint64_t)(*upto - 1) * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
+    *info_out = info;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_agg_bucket_piece_count(DevSegments s, BucketRequest r,
+                                                                 const unsigned long long *__restrict__ piece_base,
+                                                                 const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
+                                                                 unsigned long long *__restrict__ counts) {
+    const unsigned long long piece = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (piece >= n_pieces) return;
+    const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
+    const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
+    SegInfo info;
+    uint32_t from, upto;
+    uint64_t b_first, b_last;
+    counts[piece] = bucket_piece_span(s, r, piece_base, c0, c1, &info, &from, &upto, &b_first, &b_last)
+                        ? b_last - b_first + 1 : 0;
+}
+
+// Writes the entries [e0, e1) of the call (entry e at e - e0).
+__global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, BucketRequest r, const uint32_t *__restrict__ groups,
+                                                                const unsigned long long *__restrict__ piece_base,
+                                                                const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
+                                                                const unsigned long long *__restrict__ offsets,
+                                                                unsigned long long e0, unsigned long long e1,
+                                                                unsigned long long *__restrict__ keys,
+                                                                BucketPartial *__restrict__ out) {
+    __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
+    const int lane = threadIdx.x;
+    const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
+    const uint8_t *values_first = first_buffer(s.values), *residuals_first = first_buffer(s.residuals); // (see view_data())
+    uint32_t to_decode = 0, to_skip = 0, point_index = 0;
+    uint64_t b_first = 0, b_last = 0, base = 0, row = 0;
+    int64_t start = 0, delta = 0;
+    PieceReader reader;
+    PieceState state;
+    reader.idle(cursors);
+    state.last = 0; state.trailing = 0; state.window_bits = 0; state.raw = false;
+    if (piece < n_pieces && offsets[piece + 1] > e0 && offsets[piece] < e1) {
+        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
+        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
+        SegInfo info;
+        uint32_t from, upto;
+        if (bucket_piece_span(s, r, piece_base, c0, c1, &info, &from, &upto, &b_first, &b_last)) {
+            const uint32_t i = c0.z, window = c1.y;
+            point_index = c0.w;
+            const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
+            // (a tail is XOR-seeded with the model's last RECONSTRUCTED value, models/mod.rs:241-249: what grid() sees)
+            const uint32_t seed = residual ? __float_as_uint(info.desc.value) : 0u;
+            to_decode = upto - point_index;
+            to_skip = from - point_index;
+            start = info.desc.start;
+            delta = info.desc.delta;
+            base = offsets[piece];
+            row = (uint64_t)(groups ? groups[i] : 0u) * r.n_buckets;
+            const DevCol &column = residual ? s.residuals : s.values;
+            const uint4 view = column.views[i];
+            reader.open(view_data(column, i, view, residual ? residuals_first : values_first),
+                        residual ? (uint64_t)view.x - 1u : (uint64_t)view.x, c0.x);
+            state.last = seed ^ c0.y;
+            const uint32_t leading = window & 255u, trailing = (window >> 8) & 255u;
+            state.trailing = trailing & 31u;
+            state.window_bits = leading + trailing <= 32u ? 32u - leading - trailing : 0u;
+            state.raw = (window & MV_WINDOW_RAW) != 0;
+        }
+    }
+    if (!__any(to_decode > 0)) return;
+    RangePartial acc;
+    acc.clear();
+    uint64_t bucket = b_first;
+    auto flush = [&]() {
+        const uint64_t e = base + (bucket - b_first);
+        if (e >= e0 && e < e1) {
+            keys[e - e0] = row + bucket;
+            out[e - e0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
+        }
+        acc.clear();
+        bucket++;
+    };
+    auto take = [&](uint32_t k, uint32_t bits) {
+        if (k < to_skip || k >= to_decode) return;
+        const int64_t t = start + (int64_t)((uint64_t)(point_index + k) * (uint64_t)delta);
+        const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
+        while (bucket < b) flush();
+        acc.point(__uint_as_float(bits));
+    };
+    reader.begin();
+    reader.top_up(ring, lane);
+    reader.top_up(ring, lane);
+    reader.start(ring, lane);
+    for (uint32_t k = 0, most = wave_max_u32(to_decode); k < most; k += 2) {
+        if (__any(reader.hungry())) reader.top_up(ring, lane);
+        const uint32_t even = piece_decode_value(reader, state, ring, lane);
+        const uint32_t odd = piece_decode_value(reader, state, ring, lane);
+        take(k, even);
+        take(k + 1, odd);
+    }
+    if (to_decode > 0) flush(); // (bucket == b_last)
+}
+
+struct BucketPieceCountOf {
+    const unsigned long long *counts;
+    __device__ uint64_t operator()(uint64_t k) const { return counts[k]; }
+};
+
+int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
+                        const MvIndex &index, const unsigned long long **offsets_out, unsigned long long *total) {
+    *total = 0;
+    const uint64_t n = index.n_pieces;
+    void *p = nullptr;
+    const uint64_t counts_bytes = align_up(n * 8, 256), offsets_bytes = align_up((n + 1) * 8, 256);
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_PIECES, counts_bytes + offsets_bytes + scan_block_sums_bytes(n) + 256, &p))
+        return 1;
+    unsigned long long *counts = static_cast<unsigned long long *>(p);
+    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes);
+    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes + offsets_bytes);
+    {
+        LaunchTimer timer(ctx, "k_agg_bucket_piece_count");
+        hipLaunchKernelGGL(k_agg_bucket_piece_count, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, s, r,
+                           piece_base, static_cast<const MvCursor *>(index.cursors), (unsigned long long)n, counts);
+    }
+    if (device_exclusive_scan(ctx, BucketPieceCountOf{counts}, n, offsets, block_sums, "k_agg_bucket_piece_count")) return 1;
+    MDB_HIP_CHECK(hipMemcpyAsync(total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    *offsets_out = offsets;
+    return 0;
+}
+
+int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
+                          const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
+                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out) {
+    const uint64_t n = index.n_pieces;
+    LaunchTimer timer(ctx, "k_agg_bucket_pieces");
+    hipLaunchKernelGGL(k_agg_bucket_pieces, dim3((uint32_t)((n + MDB_WAVE - 1) / MDB_WAVE)), dim3(MDB_WAVE), 0, ctx->stream, s,
+                       r, groups, piece_base, static_cast<const MvCursor *>(index.cursors), (unsigned long long)n, offsets,
+                       e0, e1, keys, out);
+    return 0;
 }
 
 // One workgroup, fixed order (strided partial sums, then a fixed tree): the result does not depend

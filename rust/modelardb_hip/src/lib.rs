@@ -31,7 +31,7 @@ use arrow::datatypes::Schema;
 use arrow::record_batch::RecordBatch;
 use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
-pub use sys::{mdb_agg_state as AggState, mdb_grid_metrics as GridMetrics};
+pub use sys::{mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics};
 pub use sys::{MDB_AGG_AVG, MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM};
 
 /// Failure reported by the library (the text of `mdb_last_error()`).
@@ -340,6 +340,34 @@ impl Context {
         check(unsafe {
             sys::mdb_agg_batch_range_list(self.raw(), inputs.as_ptr(), inputs.len() as u32, t_lo, t_hi, which_mask, state)
         })
+    }
+
+    /// COUNT / MIN / MAX / SUM per bucket of `date_bin(width, ts, origin)` and group, without materialising a data
+    /// point: `states` is row-major `[n_groups][n_buckets]`, each cell folded like `mdb_agg_merge` (a cell without
+    /// points stays as it was). `group_of_segment`: one id per segment row (`None`: all in group 0).
+    pub fn agg_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        states: &mut [AggState],
+    ) -> Result<()> {
+        let cells = (request.n_groups as u64).checked_mul(request.n_buckets);
+        if cells != Some(states.len() as u64) {
+            return Err(HipError(format!(
+                "states holds {} cells, the request n_groups * n_buckets = {} * {}",
+                states.len(),
+                request.n_groups,
+                request.n_buckets
+            )));
+        }
+        if let Some(groups) = group_of_segment {
+            if groups.len() as u64 != segments.raw.n {
+                return Err(HipError(format!("{} group ids for {} segments", groups.len(), segments.raw.n)));
+            }
+        }
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_agg_buckets(self.raw(), &segments.raw, groups, request, states.as_mut_ptr()) })
     }
 
     /// Replaces the body of `try_compress_univariate_time_series` after its two argument checks

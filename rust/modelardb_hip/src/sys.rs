@@ -162,6 +162,25 @@ pub struct mdb_chunk {
     pub n: u64,
 }
 
+/// The buckets of `date_bin(width, ts, origin)` for `mdb_agg_buckets*`: bucket b holds the points with
+/// origin + b*width <= ts <= origin + (b+1)*width - 1 (floor division, also for ts < origin).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct mdb_bucket_request {
+    pub origin: i64,
+    /// > 0, in the timestamps' unit (µs).
+    pub width: i64,
+    /// Points outside buckets 0 .. n_buckets-1 are not counted.
+    pub n_buckets: u64,
+    /// Inclusive time range ANDed with the buckets (`i64::MIN` / `i64::MAX`: none).
+    pub t_lo: i64,
+    pub t_hi: i64,
+    /// >= 1.
+    pub n_groups: u32,
+    /// `MDB_AGG_*`, as in `mdb_agg_batch`.
+    pub which_mask: u32,
+}
+
 #[link(name = "mdb_hip")]
 unsafe extern "C" {
     // ---- lifetime ----------------------------------------------------------------------------
@@ -235,6 +254,13 @@ unsafe extern "C" {
                                which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
     pub fn mdb_agg_batch_range_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64,
                                    which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                           request: *const mdb_bucket_request, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                               request: *const mdb_bucket_request, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                group_of_segment: *const *const u32, n_inputs: u32,
+                                request: *const mdb_bucket_request, inout: *mut mdb_agg_state) -> c_int;
     pub fn mdb_agg_batch_range_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments, n_inputs: u32,
                                     t_lo: i64, t_hi: i64, which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
 
@@ -266,6 +292,7 @@ unsafe extern "C" {
     pub fn mdb_comm_close(ctx: *mut mdb_ctx) -> c_int;
     pub fn mdb_agg_all_reduce(ctx: *mut mdb_ctx, inout: *mut mdb_agg_state, ranks_seen: *mut i32) -> c_int;
     pub fn mdb_agg_merge(into: *mut mdb_agg_state, from: *const mdb_agg_state) -> c_int;
+    pub fn mdb_agg_merge_n(into: *mut mdb_agg_state, from: *const mdb_agg_state, n: u64) -> c_int;
 
     // ---- measurement ---------------------------------------------------------------------------------
     pub fn mdb_profile_enable(ctx: *mut mdb_ctx, enabled: c_int) -> c_int;
@@ -328,3 +355,10 @@ const _: () = assert!(offset_of!(mdb_grid_request, reserve_front) == 24);
 const _: () = assert!(size_of::<mdb_chunk>() == 24);
 const _: () = assert!(offset_of!(mdb_chunk, values) == 8);
 const _: () = assert!(offset_of!(mdb_chunk, n) == 16);
+const _: () = assert!(size_of::<mdb_bucket_request>() == 48);
+const _: () = assert!(offset_of!(mdb_bucket_request, width) == 8);
+const _: () = assert!(offset_of!(mdb_bucket_request, n_buckets) == 16);
+const _: () = assert!(offset_of!(mdb_bucket_request, t_lo) == 24);
+const _: () = assert!(offset_of!(mdb_bucket_request, t_hi) == 32);
+const _: () = assert!(offset_of!(mdb_bucket_request, n_groups) == 40);
+const _: () = assert!(offset_of!(mdb_bucket_request, which_mask) == 44);
