@@ -263,6 +263,40 @@ int mdb_agg_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs,
                          const uint32_t *const *group_of_segment, uint32_t n_inputs,
                          const mdb_bucket_request *request, mdb_agg_state *inout);
 
+/* Extension: a value predicate pushed down to the segments - WHERE field op literal [AND ts op literal ...], see
+ * mdb_value_filter (mdb_format.h). The reference rewrites only predicates on the timestamp column
+ * (query/time_series_table.rs:290-370); one on the field stays in a FilterExec above GridExec, which rebuilds every
+ * point first (query/grid_exec.rs:366-387), and an aggregate under it misses the model-based rule, whose input must
+ * be a SortedJoinExec (optimizer/model_simple_aggregates.rs:214-243).
+ *   Grid: replaces GridExec -> FilterExec. The rows are exactly those of mdb_grid_batch_range(t_lo, t_hi) without
+ *     the ones whose value fails, in segment order and point order within a segment. out_rows_per_segment (may be
+ *     NULL) counts the rows of each segment (0: none). The row counters of metrics count the rows produced, the
+ *     segment counters are mdb_grid_batch_range's for the same t_lo / t_hi.
+ *   Aggregates: replace GridExec -> FilterExec -> AggregateExec. The passing points are folded into *inout with the
+ *     rules of mdb_agg_batch_range: COUNT / MIN / MAX exact, SUM the f64 sum of the passing f32 points within the
+ *     0.001 % of the other aggregates; no passing point leaves *inout as mdb_agg_batch_range leaves it. The host,
+ *     dev and list forms agree bit for bit, and so do two runs (a fixed reduction tree, no float atomics).
+ *   An empty value interval (v_lo above v_hi in totalOrder, [c, c)) is valid and selects nothing.
+ *   Errors (mdb_last_error set, outputs untouched): unknown flag bits, reserved != 0, cap too small, and the error
+ *     classes of the range calls. */
+int mdb_grid_count_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, uint64_t *n_out);
+int mdb_grid_batch_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, int64_t *out_ts,
+                              float *out_val, uint32_t *out_rows_per_segment, uint64_t cap, uint64_t *n_out,
+                              mdb_grid_metrics *metrics);
+/* One-call form for host callers, as mdb_grid_batch_owned (one upload, the work on the device, one copy back into
+ * page-locked memory, the same reserve_front): only the passing rows and rows_per_segment cross PCIe. Freed by
+ * mdb_grid_result_free. */
+int mdb_grid_batch_filter_owned(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter,
+                                uint64_t reserve_front, mdb_grid_result **out);
+int mdb_agg_batch_filter(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, uint32_t which_mask,
+                         mdb_agg_state *inout);
+/* The segments in HBM (inout stays a host pointer, as for mdb_agg_batch_range_dev). */
+int mdb_agg_batch_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter,
+                             uint32_t which_mask, mdb_agg_state *inout);
+/* Several host batches (rows in the order of the list) folded as one batch, as mdb_agg_batch_list does. */
+int mdb_agg_batch_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs,
+                              const mdb_value_filter *filter, uint32_t which_mask, mdb_agg_state *inout);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -170,6 +170,22 @@ typedef struct mdb_bucket_request {
     uint32_t which_mask;  /* MDB_AGG_*, with the same meaning as in mdb_agg_batch */
 } mdb_bucket_request;     /* 48 bytes */
 
+/* A value predicate ANDed with a time range, for mdb_grid_*_filter* and mdb_agg_batch_filter*: a point (t, v) passes
+ * if t_lo <= t <= t_hi and v lies within [v_lo, v_hi] (ends open or absent per flags). The value bounds are compared
+ * in IEEE 754 totalOrder on the f32 bit pattern (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN): the key
+ * bits ^ ((int32_t)bits >> 31 & 0x7fffffff), compared as signed integers - the order of arrow-rs's float
+ * comparison kernels, which DataFusion's FilterExec uses. IEEE v > c (never NaN) is (c, +inf]. */
+#define MDB_VALUE_LO_OPEN 1u   /* v >  v_lo instead of v >= v_lo */
+#define MDB_VALUE_HI_OPEN 2u   /* v <  v_hi instead of v <= v_hi */
+#define MDB_VALUE_NO_LO   4u   /* no lower bound */
+#define MDB_VALUE_NO_HI   8u   /* no upper bound */
+typedef struct mdb_value_filter {
+    int64_t  t_lo, t_hi;   /* inclusive time range, ANDed (INT64_MIN / INT64_MAX: none) */
+    float    v_lo, v_hi;   /* value bounds */
+    uint32_t flags;        /* MDB_VALUE_* */
+    uint32_t reserved;     /* must be 0 */
+} mdb_value_filter;        /* 32 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -247,5 +263,11 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, t_lo) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, t_hi) == 32);
 MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, n_groups) == 40);
 MDB_LAYOUT_ASSERT(offsetof(mdb_bucket_request, which_mask) == 44);
+MDB_LAYOUT_ASSERT(sizeof(mdb_value_filter) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, t_hi) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, v_lo) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, v_hi) == 20);
+MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, flags) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, reserved) == 28);
 
 #endif /* MDB_FORMAT_H */

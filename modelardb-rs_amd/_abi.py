@@ -30,6 +30,12 @@ MDB_AGG_AVG = 16
 
 MDB_COMM_ID_BYTES = 128
 
+# mdb_value_filter flags (mdb_format.h)
+MDB_VALUE_LO_OPEN = 1
+MDB_VALUE_HI_OPEN = 2
+MDB_VALUE_NO_LO = 4
+MDB_VALUE_NO_HI = 8
+
 F32_MAX = 3.4028234663852886e38
 
 
@@ -154,6 +160,18 @@ class BucketRequestC(C.Structure):
     ]
 
 
+class ValueFilterC(C.Structure):
+    """mdb_value_filter: a time range ANDed with value bounds compared in IEEE totalOrder (MDB_VALUE_* flags)."""
+    _fields_ = [
+        ("t_lo", C.c_int64),
+        ("t_hi", C.c_int64),
+        ("v_lo", C.c_float),
+        ("v_hi", C.c_float),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 _HIP_SYMBOLS = {
     # name: (restype, argtypes)
     "mdb_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -221,6 +239,19 @@ _HIP_SYMBOLS = {
                                       C.c_void_p]),
     "mdb_agg_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
                                        C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_grid_count_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC),
+                                            C.POINTER(C.c_uint64)]),
+    "mdb_grid_batch_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                            C.POINTER(GridMetricsC)]),
+    "mdb_grid_batch_filter_owned": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_uint64,
+                                              C.POINTER(C.POINTER(GridResultC))]),
+    "mdb_agg_batch_filter": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_uint32,
+                                       C.POINTER(AggStateC)]),
+    "mdb_agg_batch_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_uint32,
+                                           C.POINTER(AggStateC)]),
+    "mdb_agg_batch_filter_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.c_uint32,
+                                            C.POINTER(ValueFilterC), C.c_uint32, C.POINTER(AggStateC)]),
     "mdb_compress_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, ErrorBoundC,
                                       C.POINTER(C.POINTER(SegmentsOwnedC))]),
     "mdb_compress_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

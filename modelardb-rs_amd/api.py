@@ -7,6 +7,7 @@ library cannot be loaded or a call fails, ``HipError`` is raised.
 """
 
 import ctypes as C
+import struct
 import time
 
 import numpy as np
@@ -136,6 +137,84 @@ def agg_merge_n(into, other):
     if lib.mdb_agg_merge_n(into.ctypes.data_as(C.c_void_p), other.ctypes.data_as(C.c_void_p), into.size) != 0:
         raise HipError(lib.mdb_last_error().decode())
     return into
+
+
+def _f64_key(x):
+    """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
+    bits = struct.unpack("<q", struct.pack("<d", x))[0]
+    return bits ^ ((bits >> 63) & 0x7FFFFFFFFFFFFFFF)
+
+
+def _f32_bits_of_key(key):
+    return (key ^ ((key >> 31) & 0x7FFFFFFF)) & 0xFFFFFFFF
+
+
+def _f64_key_of_f32(key):
+    """The f64 totalOrder key of the f32 with totalOrder key `key` (f32 -> f64 is exact and keeps the order, NaN
+    payloads included: they move up by 29 bits)."""
+    bits = _f32_bits_of_key(key)
+    if (bits >> 23) & 0xFF == 0xFF and bits & 0x7FFFFF:
+        wide = ((bits >> 31) << 63) | (0x7FF << 52) | ((bits & 0x7FFFFF) << 29)
+        wide -= 1 << 64 if wide >> 63 else 0
+        return wide ^ ((wide >> 63) & 0x7FFFFFFFFFFFFFFF)
+    return _f64_key(struct.unpack("<f", struct.pack("<I", bits))[0])
+
+
+def _first_f32_key(passes):
+    """The smallest f32 totalOrder key for which passes(f64 key of that f32) holds (monotone false..true), or None."""
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    if not passes(_f64_key_of_f32(hi)):
+        return None
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if passes(_f64_key_of_f32(mid)):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def value_filter(lo=None, hi=None, lo_open=False, hi_open=False, t_lo=None, t_hi=None):
+    """An mdb_value_filter for `lo <(=) value <(=) hi AND t_lo <= ts <= t_hi` (None: no bound). lo and hi are Python
+    floats (f64); they are converted exactly, so the filter selects exactly the f32 values v for which float(v) op
+    literal holds in f64 IEEE totalOrder (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN) - the order of arrow's
+    float comparison kernels. The f32 bounds are closed, written by bit pattern (NaN payloads included)."""
+    flags, lo_bits, hi_bits = 0, 0, 0
+    empty = False
+    if lo is None:
+        flags |= _abi.MDB_VALUE_NO_LO
+    else:
+        bound = _f64_key(float(lo))
+        key = _first_f32_key((lambda k: k > bound) if lo_open else (lambda k: k >= bound))
+        if key is None:
+            empty = True
+        else:
+            lo_bits = _f32_bits_of_key(key)
+    if hi is None:
+        flags |= _abi.MDB_VALUE_NO_HI
+    else:
+        bound = _f64_key(float(hi))
+        # the largest key that passes is one below the smallest that fails
+        key = _first_f32_key((lambda k: k >= bound) if hi_open else (lambda k: k > bound))
+        if key == -(1 << 31):
+            empty = True
+        else:
+            hi_bits = _f32_bits_of_key((1 << 31) - 1 if key is None else key - 1)
+    if empty:  # no f32 value passes: (+NaN with the largest payload, ...) is empty
+        flags = _abi.MDB_VALUE_LO_OPEN | _abi.MDB_VALUE_NO_HI
+        lo_bits = 0x7FFFFFFF
+    result = _abi.ValueFilterC(INT64_MIN if t_lo is None else int(t_lo), INT64_MAX if t_hi is None else int(t_hi),
+                               0.0, 0.0, flags, 0)
+    for field, bits in (("v_lo", lo_bits), ("v_hi", hi_bits)):
+        C.memmove(C.addressof(result) + getattr(_abi.ValueFilterC, field).offset, C.byref(C.c_uint32(bits)), 4)
+    return result
+
+
+def value_filter_bits(flt):
+    """(v_lo bits, v_hi bits) of an mdb_value_filter, as uint32 (the f32 fields read without a float conversion)."""
+    raw = C.string_at(C.addressof(flt), C.sizeof(flt))
+    return struct.unpack_from("<I", raw, _abi.ValueFilterC.v_lo.offset)[0], \
+        struct.unpack_from("<I", raw, _abi.ValueFilterC.v_hi.offset)[0]
 
 
 def is_value_within_error_bound(eb, real_value, approximate_value):
@@ -436,6 +515,81 @@ class Context:
         state = state or _abi.AggStateC.fresh()
         self._check(self.lib.mdb_agg_batch_range_dev(self.handle, C.byref(dev_segments.seg), t_lo,
                                                      t_hi, which_mask, C.byref(state)))
+        return state
+
+    # ---- value filters (mdb_value_filter: see value_filter) ------------------------------------------
+
+    def grid_filter(self, batch, flt, reserve_front=0):
+        """grid() with a value predicate and a time range pushed down (mdb_grid_batch_filter_owned): only the passing
+        rows cross PCIe. Returns copies (timestamps, values, rows_per_segment, metrics)."""
+        seg = batch.as_c()
+        out = C.POINTER(_abi.GridResultC)()
+        self._check(self.lib.mdb_grid_batch_filter_owned(self.handle, C.byref(seg), C.byref(flt), int(reserve_front),
+                                                         C.byref(out)))
+        try:
+            result = out.contents
+            n, n_segments = int(result.n), int(result.n_segments)
+
+            def copy_of(pointer, count, dtype):
+                if count == 0:
+                    return np.zeros(0, dtype=dtype)
+                buffer = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(pointer)
+                return np.frombuffer(buffer, dtype=dtype).copy()
+
+            return (copy_of(result.timestamps, n, np.int64), copy_of(result.values, n, np.float32),
+                    copy_of(result.rows_per_segment, n_segments, np.uint32), result.metrics.as_dict())
+        finally:
+            self.lib.mdb_grid_result_free(out)
+
+    def grid_count_filter_dev(self, dev_segments, flt):
+        n_out = C.c_uint64()
+        self._check(self.lib.mdb_grid_count_filter_dev(self.handle, C.byref(dev_segments.seg), C.byref(flt),
+                                                       C.byref(n_out)))
+        return n_out.value
+
+    def grid_filter_dev(self, dev_segments, flt, out_ts_ptr, out_val_ptr, cap, rows_ptr=None):
+        """mdb_grid_batch_filter_dev into device columns; returns (rows produced, metrics)."""
+        n_out = C.c_uint64()
+        metrics = _abi.GridMetricsC()
+        self._check(self.lib.mdb_grid_batch_filter_dev(
+            self.handle, C.byref(dev_segments.seg), C.byref(flt), C.c_void_p(out_ts_ptr), C.c_void_p(out_val_ptr),
+            C.c_void_p(rows_ptr), cap, C.byref(n_out), C.byref(metrics)))
+        return n_out.value, metrics.as_dict()
+
+    def grid_filter_resident(self, dev_segments, flt):
+        """The dev form on a resident batch, downloaded: (timestamps, values, rows_per_segment, metrics)."""
+        n = self.grid_count_filter_dev(dev_segments, flt)
+        out_ts, out_val = self.dev_alloc(8 * max(n, 1)), self.dev_alloc(4 * max(n, 1))
+        rows = self.dev_alloc(4 * max(len(dev_segments), 1))
+        try:
+            produced, metrics = self.grid_filter_dev(dev_segments, flt, out_ts, out_val, n, rows)
+            assert produced == n
+            return (self.download_array(out_ts, n, np.int64), self.download_array(out_val, n, np.float32),
+                    self.download_array(rows, len(dev_segments), np.uint32), metrics)
+        finally:
+            for pointer in (out_ts, out_val, rows):
+                self.dev_free(pointer)
+
+    def agg_filter(self, batch, flt, which_mask, state=None):
+        """COUNT / MIN / MAX / SUM of the points that pass `flt` (mdb_agg_batch_filter), folded into `state`."""
+        seg = batch.as_c()
+        state = state or _abi.AggStateC.fresh()
+        self._check(self.lib.mdb_agg_batch_filter(self.handle, C.byref(seg), C.byref(flt), which_mask, C.byref(state)))
+        return state
+
+    def agg_filter_list(self, batches, flt, which_mask, state=None):
+        """Several host batches folded as one (mdb_agg_batch_filter_list)."""
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        state = state or _abi.AggStateC.fresh()
+        self._check(self.lib.mdb_agg_batch_filter_list(self.handle, pointers, len(views), C.byref(flt), which_mask,
+                                                       C.byref(state)))
+        return state
+
+    def agg_filter_dev(self, dev_segments, flt, which_mask, state=None):
+        state = state or _abi.AggStateC.fresh()
+        self._check(self.lib.mdb_agg_batch_filter_dev(self.handle, C.byref(dev_segments.seg), C.byref(flt), which_mask,
+                                                      C.byref(state)))
         return state
 
     # ---- aggregates per time bucket ----------------------------------------------------------------

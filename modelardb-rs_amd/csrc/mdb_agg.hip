@@ -16,6 +16,7 @@
 #include "mdb_segment_dev.hpp"
 
 #include <cfloat>
+#include <cstring>
 #include <thread>
 
 namespace mdb {
@@ -88,6 +89,14 @@ __device__ __forceinline__ AggPartial empty_partial() {
     p.deferred = 0;
     p.deferred_values = 0;
     p.deferred_bytes = 0;
+    return p;
+}
+
+static AggPartial empty_partial_host() {
+    AggPartial p;
+    std::memset(&p, 0, sizeof(p));
+    p.min = FLT_MAX;
+    p.max = -FLT_MAX;
     return p;
 }
 
@@ -247,16 +256,18 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_finish(const AggPartial *__
 // that reach into the range, len() and - PMC-Mean / Swing without residuals - the aggregates of their points inside
 // it, as the walk of their streams has found them (ts_walk_for_aggregates; the same values in the same order as
 // segment_range's own pass over such a segment).
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_range(DevSegments s, int64_t t_lo, int64_t t_hi, uint32_t mode,
-                                                           uint32_t mv_min_values,
-                                                           AggPartial *__restrict__ partials,
-                                                           const uint32_t *__restrict__ walked_totals,
-                                                           const TsWalkRange *__restrict__ walked_ranges,
-                                                           const unsigned int *__restrict__ walked_error,
-                                                           const unsigned long long *__restrict__ indexed_piece_base,
-                                                           const TsWalkRange *__restrict__ whole_in,
-                                                           TsWalkRange *__restrict__ whole_out) {
-    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+// (the body of k_agg_range and of k_agg_filter: `pred` says which values count - every value for the range calls)
+template <typename Pred>
+__device__ __forceinline__ void agg_range_body(DevSegments s, int64_t t_lo, int64_t t_hi, uint32_t mode,
+                                               uint32_t mv_min_values,
+                                               AggPartial *__restrict__ partials,
+                                               const uint32_t *__restrict__ walked_totals,
+                                               const TsWalkRange *__restrict__ walked_ranges,
+                                               const unsigned int *__restrict__ walked_error,
+                                               const unsigned long long *__restrict__ indexed_piece_base,
+                                               const TsWalkRange *__restrict__ whole_in,
+                                               TsWalkRange *__restrict__ whole_out, const Pred &pred,
+                                               AggPartial *lds) {
     AggPartial p = empty_partial();
     if (walked_error && blockIdx.x == 0 && threadIdx.x == 0) p.error |= *walked_error;
     const TimeRange range = {t_lo, t_hi, 1};
@@ -307,7 +318,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_range(DevSegments s, int64_
                 acc.min = walked.min;
                 acc.max = walked.max;
             } else {
-                segment_range(s, i, info, t_lo, t_hi, acc, &error, tail_by_pieces);
+                segment_range(s, i, info, t_lo, t_hi, acc, &error, tail_by_pieces, pred);
             }
             p.sum += acc.sum;
             p.count += acc.count;
@@ -319,6 +330,66 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_range(DevSegments s, int64_
     }
     block_reduce(p, lds);
     if (threadIdx.x == 0) partials[blockIdx.x] = p;
+}
+
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_range(DevSegments s, int64_t t_lo, int64_t t_hi, uint32_t mode,
+                                                           uint32_t mv_min_values,
+                                                           AggPartial *__restrict__ partials,
+                                                           const uint32_t *__restrict__ walked_totals,
+                                                           const TsWalkRange *__restrict__ walked_ranges,
+                                                           const unsigned int *__restrict__ walked_error,
+                                                           const unsigned long long *__restrict__ indexed_piece_base,
+                                                           const TsWalkRange *__restrict__ whole_in,
+                                                           TsWalkRange *__restrict__ whole_out) {
+    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+    agg_range_body(s, t_lo, t_hi, mode, mv_min_values, partials, walked_totals, walked_ranges, walked_error,
+                   indexed_piece_base, whole_in, whole_out, AllValues(), lds);
+}
+
+// The filtered aggregates (mdb_agg_batch_filter*): k_agg_range's loop with a value predicate, every segment that
+// reaches into the range worked out by its own lane (no walks, cursors or deferred streams: segment_range decodes
+// the streams it needs), partials into the same fixed tree.
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_filter(DevSegments s, int64_t t_lo, int64_t t_hi, ValueKeys keys,
+                                                            AggPartial *__restrict__ partials) {
+    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+    agg_range_body(s, t_lo, t_hi, AGG_SUM_ALL, 0xffffffffu, partials, static_cast<const uint32_t *>(nullptr),
+                   static_cast<const TsWalkRange *>(nullptr), static_cast<const unsigned int *>(nullptr),
+                   static_cast<const unsigned long long *>(nullptr), static_cast<const TsWalkRange *>(nullptr),
+                   static_cast<TsWalkRange *>(nullptr), keys, lds);
+}
+
+int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const ValueKeys &keys,
+                   uint32_t which_mask, mdb_agg_state *inout) {
+    if (in->n == 0) return 0; // (as agg_run: an empty batch leaves the state as it is)
+    AggPartial host = empty_partial_host();
+    {
+        const uint32_t n_blocks = (uint32_t)std::min<uint64_t>((in->n + AGG_THREADS - 1) / AGG_THREADS, 256 * 8);
+        void *p;
+        if (scratch_reserve(ctx, SCRATCH_AGG_PARTIALS, (uint64_t)(n_blocks + 1) * sizeof(AggPartial), &p)) return 1;
+        AggPartial *partials = static_cast<AggPartial *>(p);
+        AggPartial *result = partials + n_blocks;
+        {
+            LaunchTimer timer(ctx, "k_agg_filter");
+            hipLaunchKernelGGL(k_agg_filter, dim3(n_blocks), dim3(AGG_THREADS), 0, ctx->stream, to_dev(in), t_lo, t_hi,
+                               keys, partials);
+        }
+        {
+            LaunchTimer timer(ctx, "k_agg_finish");
+            hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials, n_blocks, result);
+        }
+        MDB_HIP_CHECK(hipMemcpyAsync(&host, result, sizeof(AggPartial), hipMemcpyDeviceToHost, ctx->stream));
+        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        MDB_HIP_CHECK(hipGetLastError());
+        if (host.error) return fail(describe_error(host.error));
+    }
+    // Folded into the caller's state exactly as agg_run folds a range's.
+    if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) inout->count += host.count;
+    if (which_mask & MDB_AGG_MIN) inout->min = (inout->min != inout->min) ? host.min
+                                               : (host.min < inout->min ? host.min : inout->min);
+    if (which_mask & MDB_AGG_MAX) inout->max = (inout->max != inout->max) ? host.max
+                                               : (host.max > inout->max ? host.max : inout->max);
+    if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) inout->sum += host.sum;
+    return 0;
 }
 
 int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int64_t t_hi,

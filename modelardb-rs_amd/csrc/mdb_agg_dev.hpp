@@ -3,6 +3,7 @@
 // MacaqueV pieces in mdb_grid.hip).
 #pragma once
 
+#include "mdb_filter.hpp"
 #include "mdb_segment_dev.hpp"
 
 #include <cfloat>
@@ -26,11 +27,58 @@ __device__ __forceinline__ float model_value_at(const SegDesc &d, uint32_t type,
     return type == MDB_PMC_MEAN_ID ? d.value : (float)(d.slope * (double)t + d.intercept);
 }
 
-// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi].
+// The model points [a, b] of a PMC-Mean or Swing segment with regular timestamps, in closed form.
+__device__ __forceinline__ void model_closed_form(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b,
+                                                  RangeAcc &acc) {
+    const uint32_t n = b - a + 1;
+    const int64_t ta = d.start + (int64_t)((uint64_t)a * (uint64_t)d.delta);
+    const int64_t tb = d.start + (int64_t)((uint64_t)b * (uint64_t)d.delta);
+    const float va = model_value_at(d, type, ta);
+    const float vb = model_value_at(d, type, tb);
+    // (float)(slope * t + intercept) is monotone in t, so the extremes sit at the ends.
+    acc.min = min_num(acc.min, min_num(va, vb));
+    acc.max = max_num(acc.max, max_num(va, vb));
+    acc.count += n;
+    if (type == MDB_PMC_MEAN_ID) {
+        acc.sum += (double)d.value * (double)n;
+    } else {
+        // Sum of the line over n equally spaced points: the f64 closed form of the f32 values
+        // grid() would produce - unless it could miss their sum by more than a tenth of the
+        // 0.001 % the reference allows (integration_test.rs:1155-1171). That happens when
+        // slope * t + intercept cancels almost completely (epoch timestamps, a model that lasts
+        // microseconds, values near zero): every reconstructed point then carries rounding noise
+        // of ulp(slope * t), which averages out over the points but not over the two end points
+        // the closed form uses. The bound below is the worst case of that noise plus the f32
+        // rounding of the points; beyond it the points are summed one by one, which is exactly
+        // what the reference's plan (GridExec + filter + SUM) computes.
+        const double fa = d.slope * (double)ta + d.intercept;
+        const double fb = d.slope * (double)tb + d.intercept;
+        const double closed = (fa + fb) / 2.0 * (double)n;
+        const double magnitude = fmax(fabs(fa), fabs(fb));
+        const double cancelled = fmax(fmax(fabs(d.slope * (double)ta), fabs(d.slope * (double)tb)),
+                                      fabs(d.intercept));
+        const double worst = (double)n * (6.0e-8 * magnitude + 7.0e-46 + 2.3e-16 * cancelled);
+        if (worst <= 1.0e-6 * fabs(closed)) {
+            acc.sum += closed;
+        } else {
+            double pointwise = 0.0;
+            for (uint32_t k = a; k <= b; k++) {
+                const int64_t t = d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta);
+                pointwise += (double)model_value_at(d, type, t);
+            }
+            acc.sum += pointwise;
+        }
+    }
+}
+
+// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi] (and whose value passes `pred`: every
+// value for the range calls; a ValueKeys for the filtered ones, mdb_filter.hpp).
 // tail_by_pieces: the residual tail's points are k_agg_mv_range's (regular timestamps only).
+template <typename Pred = AllValues>
 __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, const SegInfo &info,
                                               int64_t t_lo, int64_t t_hi, RangeAcc &acc,
-                                              uint32_t *error, bool tail_by_pieces = false) {
+                                              uint32_t *error, bool tail_by_pieces = false,
+                                              const Pred &pred = Pred()) {
     const SegDesc &d = info.desc;
     const uint32_t type = d.flags & FLAG_TYPE_MASK;
     const int64_t end = s.end_time[i];
@@ -44,7 +92,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error,
                                         [&](uint32_t, int64_t t) {
                                             if (t >= t_lo && t <= t_hi)
-                                                acc.point(model_value_at(d, type, t));
+                                                { const float v = model_value_at(d, type, t); if (pred.pass(v)) acc.point(v); }
                                         });
             return;
         }
@@ -66,7 +114,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             uint32_t last_bits = 0;
             decode_macaque_v(view_data(s.values, i, vv), vv.x, d.n_model, false, 0, error,
                              [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) acc.point(__uint_as_float(bits));
+                                 if (k >= k_lo && k <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
                                  last_bits = bits;
                              });
             seed = __uint_as_float(last_bits);
@@ -74,7 +122,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, d.n_model, error,
                                         [&](uint32_t k, int64_t t) {
                                             if (k >= k_lo && k <= k_hi)
-                                                acc.point(model_value_at(d, type, t));
+                                                { const float v = model_value_at(d, type, t); if (pred.pass(v)) acc.point(v); }
                                         });
         }
         if (n_res > 0) {
@@ -82,7 +130,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, n_res, true,
                              __float_as_uint(seed), error, [&](uint32_t k, uint32_t bits) {
                                  uint32_t index = d.n_model + k;
-                                 if (index >= k_lo && index <= k_hi) acc.point(__uint_as_float(bits));
+                                 if (index >= k_lo && index <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
                              });
         }
         return;
@@ -96,43 +144,19 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
     if (type != MDB_MACAQUE_V_ID && k_lo < d.n_model) {
         const uint32_t a = k_lo;
         const uint32_t b = min(k_hi, d.n_model - 1);
-        const uint32_t n = b - a + 1;
-        const int64_t ta = d.start + (int64_t)((uint64_t)a * (uint64_t)d.delta);
-        const int64_t tb = d.start + (int64_t)((uint64_t)b * (uint64_t)d.delta);
-        const float va = model_value_at(d, type, ta);
-        const float vb = model_value_at(d, type, tb);
-        // (float)(slope * t + intercept) is monotone in t, so the extremes sit at the ends.
-        acc.min = min_num(acc.min, min_num(va, vb));
-        acc.max = max_num(acc.max, max_num(va, vb));
-        acc.count += n;
-        if (type == MDB_PMC_MEAN_ID) {
-            acc.sum += (double)d.value * (double)n;
+        if constexpr (Pred::always) {
+            model_closed_form(d, type, a, b, acc);
         } else {
-            // Sum of the line over n equally spaced points: the f64 closed form of the f32 values
-            // grid() would produce - unless it could miss their sum by more than a tenth of the
-            // 0.001 % the reference allows (integration_test.rs:1155-1171). That happens when
-            // slope * t + intercept cancels almost completely (epoch timestamps, a model that lasts
-            // microseconds, values near zero): every reconstructed point then carries rounding noise
-            // of ulp(slope * t), which averages out over the points but not over the two end points
-            // the closed form uses. The bound below is the worst case of that noise plus the f32
-            // rounding of the points; beyond it the points are summed one by one, which is exactly
-            // what the reference's plan (GridExec + filter + SUM) computes.
-            const double fa = d.slope * (double)ta + d.intercept;
-            const double fb = d.slope * (double)tb + d.intercept;
-            const double closed = (fa + fb) / 2.0 * (double)n;
-            const double magnitude = fmax(fabs(fa), fabs(fb));
-            const double cancelled = fmax(fmax(fabs(d.slope * (double)ta), fabs(d.slope * (double)tb)),
-                                          fabs(d.intercept));
-            const double worst = (double)n * (6.0e-8 * magnitude + 7.0e-46 + 2.3e-16 * cancelled);
-            if (worst <= 1.0e-6 * fabs(closed)) {
-                acc.sum += closed;
-            } else {
-                double pointwise = 0.0;
+            // The passing points of the model part: none, one interval in closed form, or (an end is NaN) one by one.
+            uint32_t ra = a, rb = b;
+            const int run = model_run(d, type, a, b, pred, &ra, &rb);
+            if (run == RUN_INTERVAL) {
+                model_closed_form(d, type, ra, rb, acc);
+            } else if (run == RUN_POINTS) {
                 for (uint32_t k = a; k <= b; k++) {
-                    const int64_t t = d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta);
-                    pointwise += (double)model_value_at(d, type, t);
+                    const float v = model_value_at(d, type, d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta));
+                    if (pred.pass(v)) acc.point(v);
                 }
-                acc.sum += pointwise;
             }
         }
     }
@@ -146,7 +170,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
         if (k_lo < d.n_model || residuals_in_range) {
             decode_macaque_v(view_data(s.values, i, vv), vv.x, upto, false, 0, error,
                              [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) acc.point(__uint_as_float(bits));
+                                 if (k >= k_lo && k <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
                                  last_bits = bits;
                              });
         }
@@ -158,7 +182,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
         decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, upto, true, __float_as_uint(seed),
                          error, [&](uint32_t k, uint32_t bits) {
                              uint32_t index = d.n_model + k;
-                             if (index >= k_lo) acc.point(__uint_as_float(bits));
+                             if (index >= k_lo) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
                          });
     }
 }

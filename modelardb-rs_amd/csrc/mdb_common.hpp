@@ -89,6 +89,9 @@ enum ScratchSlot {
     SCRATCH_BUCKET_CELLS, // ... the working copy of the caller's cells (host forms, several slices)
     SCRATCH_BUCKET_GROUPS, // ... the group ids of the host forms
     SCRATCH_BUCKET_PIECES, // ... entry counts and offsets of the MacaqueV pieces (mdb_grid.hip)
+    SCRATCH_FILTER_SEGMENTS, // mdb_grid_*_filter*: per segment its interval, row count, offsets and the scans
+    SCRATCH_FILTER_GATHER,   // ... the columns of the segments whose points are tested one by one
+    SCRATCH_FILTER_SLICE,    // ... one slice of their rebuilt points
     SCRATCH_SLOT_COUNT
 };
 

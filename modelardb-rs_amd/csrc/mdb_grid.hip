@@ -4720,6 +4720,16 @@ int grid_batch_dev_locked(mdb_ctx *ctx, const mdb_segments *in, TimeRange range,
     return grid_late_error(ctx, plan);
 }
 
+int grid_range_plan(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, uint64_t *total,
+                    mdb_grid_metrics *metrics, uint32_t *rows_per_segment) {
+    GridPlan plan;
+    if (grid_plan(ctx, in, TimeRange{t_lo, t_hi, 1}, &plan)) return 1;
+    *total = plan.host_header.total_points;
+    fill_metrics(plan.host_header, metrics);
+    if (rows_per_segment && grid_offsets(ctx, in, rows_per_segment, &plan)) return 1;
+    return 0;
+}
+
 } // namespace mdb
 
 using namespace mdb;

@@ -31,7 +31,11 @@ use arrow::datatypes::Schema;
 use arrow::record_batch::RecordBatch;
 use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
-pub use sys::{mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics};
+pub use sys::{
+    mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
+    mdb_value_filter as ValueFilter,
+};
+pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_AGG_AVG, MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM};
 
 /// Failure reported by the library (the text of `mdb_last_error()`).
@@ -224,6 +228,49 @@ impl<'a> SegmentsView<'a> {
     }
 }
 
+impl ValueFilter {
+    /// Every value of every timestamp: narrow it with [`ValueFilter::time`], [`ValueFilter::above`] and
+    /// [`ValueFilter::below`]. For `WHERE field op literal` the caller converts the literal to the f32 bound that
+    /// selects the same f32 values (the Python binding's `value_filter` does so exactly, NaN and ±0 included).
+    pub fn all() -> Self {
+        ValueFilter {
+            t_lo: i64::MIN,
+            t_hi: i64::MAX,
+            v_lo: 0.0,
+            v_hi: 0.0,
+            flags: MDB_VALUE_NO_LO | MDB_VALUE_NO_HI,
+            reserved: 0,
+        }
+    }
+
+    /// ANDs `t_lo <= timestamp <= t_hi`.
+    pub fn time(mut self, t_lo: i64, t_hi: i64) -> Self {
+        self.t_lo = t_lo;
+        self.t_hi = t_hi;
+        self
+    }
+
+    /// `value >= v_lo` (`open`: `value > v_lo`), in totalOrder.
+    pub fn above(mut self, v_lo: f32, open: bool) -> Self {
+        self.v_lo = v_lo;
+        self.flags &= !(MDB_VALUE_NO_LO | MDB_VALUE_LO_OPEN);
+        if open {
+            self.flags |= MDB_VALUE_LO_OPEN;
+        }
+        self
+    }
+
+    /// `value <= v_hi` (`open`: `value < v_hi`), in totalOrder.
+    pub fn below(mut self, v_hi: f32, open: bool) -> Self {
+        self.v_hi = v_hi;
+        self.flags &= !(MDB_VALUE_NO_HI | MDB_VALUE_HI_OPEN);
+        if open {
+            self.flags |= MDB_VALUE_HI_OPEN;
+        }
+        self
+    }
+}
+
 /// The block of page-locked memory `mdb_grid_batch_owned` reconstructed a batch into. Arrow buffers
 /// made from it keep it alive; the last one to go returns it to the library's pool.
 struct GridBlock(NonNull<sys::mdb_grid_result>);
@@ -246,6 +293,38 @@ pub struct GridOutput {
     /// Data points each segment row reconstructed to, for the tag replication of grid_exec.rs:341-346.
     pub rows_per_segment: Vec<u32>,
     pub metrics: GridMetrics,
+}
+
+/// The arrays of an owned grid result (`mdb_grid_batch_owned` / `mdb_grid_batch_filter_owned`), the leftovers copied
+/// into the room in front of the new points.
+fn grid_output(raw: *mut sys::mdb_grid_result, leftover_timestamps: &[i64], leftover_values: &[f32]) -> GridOutput {
+    let leftovers = leftover_timestamps.len();
+    let block = Arc::new(GridBlock(NonNull::new(raw).expect("success with a null result")));
+    let result = unsafe { block.0.as_ref() };
+    let total = leftovers + result.n as usize;
+    let rows_per_segment =
+        unsafe { std::slice::from_raw_parts(result.rows_per_segment, result.n_segments as usize) }.to_vec();
+    let (timestamps, values) = unsafe {
+        // `reserve_front` rows of writable room sit in front of the new points.
+        let first_timestamp = result.timestamps.sub(leftovers);
+        let first_value = result.values.sub(leftovers);
+        ptr::copy_nonoverlapping(leftover_timestamps.as_ptr(), first_timestamp, leftovers);
+        ptr::copy_nonoverlapping(leftover_values.as_ptr(), first_value, leftovers);
+        let timestamps = Buffer::from_custom_allocation(
+            NonNull::new_unchecked(first_timestamp.cast::<u8>()),
+            8 * total,
+            block.clone(),
+        );
+        let values =
+            Buffer::from_custom_allocation(NonNull::new_unchecked(first_value.cast::<u8>()), 4 * total, block.clone());
+        (timestamps, values)
+    };
+    GridOutput {
+        timestamps: TimestampArray::new(ScalarBuffer::new(timestamps, 0, total), None),
+        values: ValueArray::new(ScalarBuffer::new(values, 0, total), None),
+        rows_per_segment,
+        metrics: result.metrics,
+    }
 }
 
 impl Context {
@@ -271,31 +350,50 @@ impl Context {
         check(unsafe {
             sys::mdb_grid_batch_owned(self.raw(), &segments.raw, flags, t_lo, t_hi, leftovers as u64, &mut raw)
         })?;
-        let block = Arc::new(GridBlock(NonNull::new(raw).expect("success with a null result")));
-        let result = unsafe { block.0.as_ref() };
-        let total = leftovers + result.n as usize;
-        let rows_per_segment =
-            unsafe { std::slice::from_raw_parts(result.rows_per_segment, result.n_segments as usize) }.to_vec();
-        let (timestamps, values) = unsafe {
-            // `reserve_front` rows of writable room sit in front of the new points.
-            let first_timestamp = result.timestamps.sub(leftovers);
-            let first_value = result.values.sub(leftovers);
-            ptr::copy_nonoverlapping(leftover_timestamps.as_ptr(), first_timestamp, leftovers);
-            ptr::copy_nonoverlapping(leftover_values.as_ptr(), first_value, leftovers);
-            let timestamps = Buffer::from_custom_allocation(
-                NonNull::new_unchecked(first_timestamp.cast::<u8>()),
-                8 * total,
-                block.clone(),
-            );
-            let values =
-                Buffer::from_custom_allocation(NonNull::new_unchecked(first_value.cast::<u8>()), 4 * total, block.clone());
-            (timestamps, values)
-        };
-        Ok(GridOutput {
-            timestamps: TimestampArray::new(ScalarBuffer::new(timestamps, 0, total), None),
-            values: ValueArray::new(ScalarBuffer::new(values, 0, total), None),
-            rows_per_segment,
-            metrics: result.metrics,
+        Ok(grid_output(raw, leftover_timestamps, leftover_values))
+    }
+
+    /// [`Context::grid`] with a value predicate and a time range pushed down (`mdb_grid_batch_filter_owned`):
+    /// replaces GridExec -> FilterExec (grid_exec.rs:366-387 and the FilterExec DataFusion keeps above it for a
+    /// predicate on the field column). Only the passing rows cross PCIe; `rows_per_segment` counts them per segment.
+    pub fn grid_filter_owned(
+        &self,
+        segments: &SegmentsView,
+        filter: &ValueFilter,
+        leftover_timestamps: &[i64],
+        leftover_values: &[f32],
+    ) -> Result<GridOutput> {
+        assert_eq!(leftover_timestamps.len(), leftover_values.len());
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::mdb_grid_batch_filter_owned(self.raw(), &segments.raw, filter, leftover_timestamps.len() as u64, &mut raw)
+        })?;
+        Ok(grid_output(raw, leftover_timestamps, leftover_values))
+    }
+
+    /// COUNT / MIN / MAX / SUM of the points that pass `filter`, folded into `state` without materialising a data
+    /// point: replaces GridExec -> FilterExec -> AggregateExec.
+    pub fn agg_filter(
+        &self,
+        segments: &SegmentsView,
+        filter: &ValueFilter,
+        which_mask: u32,
+        state: &mut AggState,
+    ) -> Result<()> {
+        check(unsafe { sys::mdb_agg_batch_filter(self.raw(), &segments.raw, filter, which_mask, state) })
+    }
+
+    /// [`Context::agg_filter`] for several batches at once (rows in the order of the slice), folded as one batch.
+    pub fn agg_filter_list(
+        &self,
+        segments: &[SegmentsView],
+        filter: &ValueFilter,
+        which_mask: u32,
+        state: &mut AggState,
+    ) -> Result<()> {
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_agg_batch_filter_list(self.raw(), inputs.as_ptr(), inputs.len() as u32, filter, which_mask, state)
         })
     }
 

@@ -181,6 +181,29 @@ pub struct mdb_bucket_request {
     pub which_mask: u32,
 }
 
+/// `mdb_value_filter` flags: an open lower / upper end, or none at all.
+pub const MDB_VALUE_LO_OPEN: u32 = 1;
+pub const MDB_VALUE_HI_OPEN: u32 = 2;
+pub const MDB_VALUE_NO_LO: u32 = 4;
+pub const MDB_VALUE_NO_HI: u32 = 8;
+
+/// A value predicate ANDed with a time range for `mdb_grid_*_filter*` / `mdb_agg_batch_filter*`: a point passes if
+/// t_lo <= t <= t_hi and its value lies within [v_lo, v_hi] (ends per `flags`), compared in IEEE 754 totalOrder on the
+/// f32 bit pattern (-NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN), the order of arrow-rs's float kernels.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_value_filter {
+    /// Inclusive time range (`i64::MIN` / `i64::MAX`: none).
+    pub t_lo: i64,
+    pub t_hi: i64,
+    pub v_lo: f32,
+    pub v_hi: f32,
+    /// `MDB_VALUE_*`.
+    pub flags: u32,
+    /// Must be 0.
+    pub reserved: u32,
+}
+
 #[link(name = "mdb_hip")]
 unsafe extern "C" {
     // ---- lifetime ----------------------------------------------------------------------------
@@ -261,6 +284,20 @@ unsafe extern "C" {
     pub fn mdb_agg_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
                                 group_of_segment: *const *const u32, n_inputs: u32,
                                 request: *const mdb_bucket_request, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_grid_count_filter_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                                     n_out: *mut u64) -> c_int;
+    pub fn mdb_grid_batch_filter_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                                     out_ts: *mut i64, out_val: *mut f32, out_rows_per_segment: *mut u32, cap: u64,
+                                     n_out: *mut u64, metrics: *mut mdb_grid_metrics) -> c_int;
+    pub fn mdb_grid_batch_filter_owned(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                                       reserve_front: u64, out: *mut *mut mdb_grid_result) -> c_int;
+    pub fn mdb_agg_batch_filter(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                                which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_batch_filter_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                                    which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_batch_filter_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments, n_inputs: u32,
+                                     filter: *const mdb_value_filter, which_mask: u32,
+                                     inout: *mut mdb_agg_state) -> c_int;
     pub fn mdb_agg_batch_range_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments, n_inputs: u32,
                                     t_lo: i64, t_hi: i64, which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
 
@@ -362,3 +399,9 @@ const _: () = assert!(offset_of!(mdb_bucket_request, t_lo) == 24);
 const _: () = assert!(offset_of!(mdb_bucket_request, t_hi) == 32);
 const _: () = assert!(offset_of!(mdb_bucket_request, n_groups) == 40);
 const _: () = assert!(offset_of!(mdb_bucket_request, which_mask) == 44);
+const _: () = assert!(size_of::<mdb_value_filter>() == 32);
+const _: () = assert!(offset_of!(mdb_value_filter, t_hi) == 8);
+const _: () = assert!(offset_of!(mdb_value_filter, v_lo) == 16);
+const _: () = assert!(offset_of!(mdb_value_filter, v_hi) == 20);
+const _: () = assert!(offset_of!(mdb_value_filter, flags) == 24);
+const _: () = assert!(offset_of!(mdb_value_filter, reserved) == 28);
