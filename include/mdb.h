@@ -297,6 +297,32 @@ int mdb_agg_batch_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_val
 int mdb_agg_batch_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs,
                               const mdb_value_filter *filter, uint32_t which_mask, mdb_agg_state *inout);
 
+/* Extension: mdb_agg_buckets* with a value predicate - SELECT <tags>, date_bin(...), AGG(field) ... WHERE field op
+ * literal [AND ts op literal ...] GROUP BY 1, 2, which the reference answers with GridExec -> FilterExec ->
+ * AggregateExec. A point (t, v) of segment row i counts in cell (group_of_segment[i], floor((t - origin) / width))
+ * when that bucket is in [0, n_buckets), t lies in both [request->t_lo, request->t_hi] and [filter->t_lo,
+ * filter->t_hi], and v passes the filter's value bounds in totalOrder (as for mdb_agg_batch_filter).
+ *   The result is mdb_agg_buckets of the same batch with every other point removed: the same fold rules, the same
+ *     pairs, entries and reduction tree; a cell without a passing point is left exactly as it was. COUNT, MIN and
+ *     MAX are exact, SUM within 0.001 %. A filter with MDB_VALUE_NO_LO | MDB_VALUE_NO_HI over the whole time range
+ *     gives the cells of mdb_agg_buckets bit for bit on a batch of finite values.
+ *   Determinism: as mdb_agg_buckets (the three forms and two runs agree bit for bit; no float atomics).
+ *   Errors (mdb_last_error set, inout untouched): a NULL argument; unknown filter flag bits or reserved != 0 (checked
+ *     before the device is used); every error of mdb_agg_buckets for the same request with its time range narrowed
+ *     to the intersection - a predicate never hides a bad group id or a malformed segment. An empty value interval
+ *     or an empty intersection of the time ranges is valid: it selects nothing, the group ids are still checked. */
+int mdb_agg_buckets_filter(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                           const mdb_bucket_request *request, const mdb_value_filter *filter, mdb_agg_state *inout);
+/* All device pointers but request and filter: the segments, group_of_segment and inout are in HBM. */
+int mdb_agg_buckets_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                               const mdb_bucket_request *request, const mdb_value_filter *filter,
+                               mdb_agg_state *inout);
+/* Several host batches (rows in the order of the list) folded as one batch, as mdb_agg_buckets_list does. */
+int mdb_agg_buckets_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs,
+                                const uint32_t *const *group_of_segment, uint32_t n_inputs,
+                                const mdb_bucket_request *request, const mdb_value_filter *filter,
+                                mdb_agg_state *inout);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

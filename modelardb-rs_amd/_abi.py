@@ -252,6 +252,13 @@ _HIP_SYMBOLS = {
                                            C.POINTER(AggStateC)]),
     "mdb_agg_batch_filter_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.c_uint32,
                                             C.POINTER(ValueFilterC), C.c_uint32, C.POINTER(AggStateC)]),
+    "mdb_agg_buckets_filter": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                         C.POINTER(ValueFilterC), C.c_void_p]),
+    "mdb_agg_buckets_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p,
+                                             C.POINTER(BucketRequestC), C.POINTER(ValueFilterC), C.c_void_p]),
+    "mdb_agg_buckets_filter_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                              C.c_uint32, C.POINTER(BucketRequestC), C.POINTER(ValueFilterC),
+                                              C.c_void_p]),
     "mdb_compress_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, ErrorBoundC,
                                       C.POINTER(C.POINTER(SegmentsOwnedC))]),
     "mdb_compress_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

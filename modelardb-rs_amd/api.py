@@ -629,6 +629,41 @@ class Context:
                          which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
                          states=None, n_groups=None):
         """Several host batches folded as one (mdb_agg_buckets_list); `groups`: None or one array (or None) per batch."""
+        return self._buckets_list(None, batches, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states,
+                                  n_groups)
+
+    def agg_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                        which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                        states=None, n_groups=None):
+        """mdb_agg_buckets_dev on a resident batch: `groups` and `states` are uploaded, the states downloaded again."""
+        return self._buckets_dev(None, dev_segments, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states,
+                                 n_groups)
+
+    def agg_buckets_filter(self, batch, flt, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                           which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                           states=None, n_groups=None):
+        """agg_buckets of the points that pass `flt`, an mdb_value_filter (value_filter), whose time range is ANDed
+        with [t_lo, t_hi] (mdb_agg_buckets_filter)."""
+        return self.agg_buckets_filter_list([batch], flt, origin, width, n_buckets,
+                                            None if groups is None else [groups], t_lo, t_hi, which_mask, states,
+                                            n_groups)
+
+    def agg_buckets_filter_list(self, batches, flt, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                                which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                                states=None, n_groups=None):
+        """Several host batches folded as one (mdb_agg_buckets_filter_list)."""
+        return self._buckets_list(flt, batches, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states,
+                                  n_groups)
+
+    def agg_buckets_filter_dev(self, dev_segments, flt, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                               which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
+                               states=None, n_groups=None):
+        """mdb_agg_buckets_filter_dev on a resident batch, as agg_buckets_dev."""
+        return self._buckets_dev(flt, dev_segments, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states,
+                                 n_groups)
+
+    def _buckets_list(self, flt, batches, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states, n_groups):
+        # (mdb_agg_buckets_list, or mdb_agg_buckets_filter_list when a filter is given)
         batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
                                                                      for g, b in zip(groups, batches)]
         n_groups = self._n_groups(n_groups, states, batch_groups)
@@ -638,14 +673,18 @@ class Context:
         pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
         group_pointers = (C.c_void_p * max(len(views), 1))(
             *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
-        self._check(self.lib.mdb_agg_buckets_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
-                                                  states.ctypes.data_as(C.c_void_p)))
+        cells = states.ctypes.data_as(C.c_void_p)
+        if flt is None:
+            self._check(self.lib.mdb_agg_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                      C.byref(request), cells))
+        else:
+            self._check(self.lib.mdb_agg_buckets_filter_list(self.handle, pointers, group_pointers, len(views),
+                                                             C.byref(request), C.byref(flt), cells))
         return states
 
-    def agg_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
-                        which_mask=_abi.MDB_AGG_COUNT | _abi.MDB_AGG_MIN | _abi.MDB_AGG_MAX | _abi.MDB_AGG_SUM,
-                        states=None, n_groups=None):
-        """mdb_agg_buckets_dev on a resident batch: `groups` and `states` are uploaded, the states downloaded again."""
+    def _buckets_dev(self, flt, dev_segments, origin, width, n_buckets, groups, t_lo, t_hi, which_mask, states,
+                     n_groups):
+        # (mdb_agg_buckets_dev, or mdb_agg_buckets_filter_dev when a filter is given)
         groups = self._groups_array(groups, len(dev_segments))
         n_groups = self._n_groups(n_groups, states, [groups])
         states = self._bucket_states(states, n_groups, n_buckets)
@@ -653,9 +692,13 @@ class Context:
         dev_groups = None if groups is None else self.upload_array(groups)
         dev_states = self.upload_array(states)
         try:
-            self._check(self.lib.mdb_agg_buckets_dev(self.handle, C.byref(dev_segments.seg),
-                                                     None if dev_groups is None else C.c_void_p(dev_groups),
-                                                     C.byref(request), C.c_void_p(dev_states)))
+            group_pointer = None if dev_groups is None else C.c_void_p(dev_groups)
+            if flt is None:
+                self._check(self.lib.mdb_agg_buckets_dev(self.handle, C.byref(dev_segments.seg), group_pointer,
+                                                         C.byref(request), C.c_void_p(dev_states)))
+            else:
+                self._check(self.lib.mdb_agg_buckets_filter_dev(self.handle, C.byref(dev_segments.seg), group_pointer,
+                                                                C.byref(request), C.byref(flt), C.c_void_p(dev_states)))
             states[...] = self.download_array(dev_states, states.size, AGG_STATE_DTYPE).reshape(states.shape)
         finally:
             self.dev_free(dev_states)

@@ -273,11 +273,13 @@ __device__ __forceinline__ bool bucket_tail_by_pieces(const DevSegments &s, uint
 }
 
 // mdb_grid.hip: the entries of the MacaqueV pieces taken above. bucket_pieces_count sizes them (offsets: per piece of
-// the index, n_pieces + 1, in scratch); bucket_pieces_entries writes the entries [e0, e1) to keys / out (at e - e0).
+// the index, n_pieces + 1, in scratch); bucket_pieces_entries writes the entries [e0, e1) to keys / out (at e - e0),
+// with the values that pass `filter` only (nullptr: every value; the entries are the same either way).
 int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
                         const MvIndex &index, const unsigned long long **offsets, unsigned long long *total);
 int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
                           const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
-                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out);
+                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
+                          const ValueKeys *filter);
 
 } // namespace mdb

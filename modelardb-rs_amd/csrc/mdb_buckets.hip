@@ -77,10 +77,12 @@ struct BucketCountOf {
 // slice, buckets b_first + (j - off). Pass 1 leaves each slot's index interval [k_lo, k_hi] of points in its sum
 // field (k_lo > k_hi: no point); pass 2 decodes the values once, each into the slot whose interval holds it, and
 // overwrites every slot with its partial. Returns false when the timestamps turn out not to be sorted (a malformed
-// stream): the caller then overwrites the slots with segment_range pair by pair, which tests every point.
+// stream): the caller then overwrites the slots with segment_range pair by pair, which tests every point. `pred` is
+// tested where a point is accumulated, nowhere else: the slots, the decode and the tail's seed are the unfiltered ones.
+template <typename Pred>
 __device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const SegInfo &info, const BucketRequest &r,
                                        uint64_t off, uint64_t b_first, uint64_t j0, uint64_t j1, uint64_t p0,
-                                       BucketPartial *__restrict__ out, uint32_t *error) {
+                                       BucketPartial *__restrict__ out, uint32_t *error, const Pred &pred) {
     const SegDesc &d = info.desc;
     const uint32_t type = d.flags & FLAG_TYPE_MASK;
     const int64_t end = s.end_time[i];
@@ -138,7 +140,7 @@ __device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const S
     };
     auto visit = [&](uint32_t k, float v) {
         while (j < j1 && k > current.y) flush();
-        if (j < j1 && k >= current.x) acc.point(v);
+        if (j < j1 && k >= current.x && pred.pass(v)) acc.point(v);
     };
     if (needed > 0) {
         float seed = d.value;
@@ -169,6 +171,9 @@ __device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const S
     return true;
 }
 
+// Pred: AllValues for mdb_agg_buckets*, ValueKeys for mdb_agg_buckets_filter* (which points of a pair count; the pairs,
+// keys and decodes are the same).
+template <typename Pred>
 __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegments s,
                                                                         const uint32_t *__restrict__ groups,
                                                                         BucketRequest r,
@@ -177,7 +182,8 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegme
                                                                         BucketPartial *__restrict__ out,
                                                                         unsigned long long *__restrict__ keys,
                                                                         unsigned int *__restrict__ error_out,
-                                                                        const unsigned long long *__restrict__ piece_base) {
+                                                                        const unsigned long long *__restrict__ piece_base,
+                                                                        Pred pred) {
     const uint64_t i = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
     if (i >= s.n) return;
     const uint64_t off = offsets[i], stop = offsets[i + 1];
@@ -195,12 +201,12 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegme
     } else if (!error) {
         const bool tail_by_pieces = bucket_tail_by_pieces(s, i, info, piece_base); // (the model's points only, then)
         const bool stream = !(info.desc.flags & FLAG_REGULAR) || (info.desc.flags & FLAG_TYPE_MASK) == MDB_MACAQUE_V_ID;
-        if (!stream || !bucket_stream_partials(s, i, info, r, off, b_first, j0, j1, p0, out, &error)) {
+        if (!stream || !bucket_stream_partials(s, i, info, r, off, b_first, j0, j1, p0, out, &error, pred)) {
             for (uint64_t j = j0; j < j1; j++) {
                 int64_t lo, hi;
                 bucket_bounds(r, b_first + (j - off), &lo, &hi);
                 RangeAcc acc;
-                segment_range(s, i, info, lo, hi, acc, &error, tail_by_pieces);
+                segment_range(s, i, info, lo, hi, acc, &error, tail_by_pieces, pred);
                 out[j - p0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
             }
         }
@@ -304,9 +310,11 @@ static int bucket_request_check(const mdb_bucket_request *request, uint64_t *n_c
 
 // The buckets of the device batch `in` (groups: a device array or nullptr) folded into `cells_target`, a device array
 // of n_cells states. `host_cells` (host forms): the caller's array, which is uploaded, folded and downloaded instead;
-// either way nothing of the caller's is written unless the whole call succeeds.
+// either way nothing of the caller's is written unless the whole call succeeds. `filter` (nullptr: every value) is the
+// value predicate of mdb_agg_buckets_filter*: only k_agg_bucket_partials and k_agg_bucket_pieces see it.
 int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, const mdb_bucket_request *request,
-                uint64_t n_cells, mdb_agg_state *dev_cells, mdb_agg_state *host_cells) {
+                uint64_t n_cells, mdb_agg_state *dev_cells, mdb_agg_state *host_cells,
+                const ValueKeys *filter = nullptr) {
     const uint64_t n = in->n;
     if (n == 0 || request->n_buckets == 0) return 0;
     const BucketRequest r = {request->origin, request->width, request->n_buckets, request->t_lo, request->t_hi,
@@ -385,11 +393,17 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
         const uint64_t p0 = (pairs ? k : k - pair_slices) * slice;
         const uint64_t p1 = std::min<uint64_t>(p0 + slice, pairs ? total : entries), m = p1 - p0;
         MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
-        if (pairs) {
+        if (pairs && filter) {
+            LaunchTimer timer(ctx, "k_agg_bucket_partials_filter");
+            hipLaunchKernelGGL(k_agg_bucket_partials<ValueKeys>, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0,
+                               ctx->stream, s, groups, r, offsets, p0, p1, partials, keys, words, piece_base, *filter);
+        } else if (pairs) {
             LaunchTimer timer(ctx, "k_agg_bucket_partials");
-            hipLaunchKernelGGL(k_agg_bucket_partials, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s,
-                               groups, r, offsets, p0, p1, partials, keys, words, piece_base);
-        } else if (bucket_pieces_entries(ctx, s, r, groups, piece_base, *index, entry_offsets, p0, p1, keys, partials)) {
+            hipLaunchKernelGGL(k_agg_bucket_partials<AllValues>, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0,
+                               ctx->stream, s, groups, r, offsets, p0, p1, partials, keys, words, piece_base,
+                               AllValues());
+        } else if (bucket_pieces_entries(ctx, s, r, groups, piece_base, *index, entry_offsets, p0, p1, keys, partials,
+                                         filter)) {
             return 1;
         }
         if (m > 1) {
@@ -462,6 +476,20 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
     return 0;
 }
 
+// The host-side checks of the filtered forms, before the device is used: the request's and the filter's own, then the
+// request with its time range narrowed to the intersection with the filter's (an empty intersection selects nothing
+// but still has its group ids checked: buckets_run runs as for any range).
+static int bucket_filter_check(const mdb_bucket_request *request, const mdb_value_filter *filter, uint64_t *n_cells,
+                               ValueKeys *keys, mdb_bucket_request *narrowed) {
+    if (bucket_request_check(request, n_cells)) return 1;
+    if (!value_keys_fold(*filter, keys))
+        return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
+    *narrowed = *request;
+    narrowed->t_lo = std::max(request->t_lo, filter->t_lo);
+    narrowed->t_hi = std::min(request->t_hi, filter->t_hi);
+    return 0;
+}
+
 // The group ids of the host forms, uploaded next to the batch (nullptr: every segment in group 0).
 static int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs,
                          uint64_t n, const uint32_t **out) {
@@ -482,6 +510,31 @@ static int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint
     }
     *out = dev;
     return 0;
+}
+
+// (the host forms of both calls: `filter` nullptr for mdb_agg_buckets*, else the folded keys and narrowed request)
+static int buckets_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                            uint32_t n_inputs, const mdb_bucket_request *request, uint64_t n_cells,
+                            const ValueKeys *filter, mdb_agg_state *inout) {
+    std::vector<uint64_t> rows(n_inputs);
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < n_inputs; k++) {
+        if (!inputs[k]) return fail("A batch of the list is NULL.");
+        rows[k] = inputs[k]->n;
+        n += rows[k];
+    }
+    if (n == 0 || request->n_buckets == 0) return 0;
+    mdb::CallGuard lock(ctx);
+    MDB_HIP_CHECK(hipSetDevice(ctx->device));
+    // (an upload the library holds, not its transient scratch: the batch then gets the cursor index a resident batch
+    // gets, and the host and device forms decode the same streams the same way - bit-identical results)
+    mdb_segments_owned *dev = nullptr;
+    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
+    const uint32_t *groups = nullptr;
+    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
+    if (!rc) rc = buckets_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout, filter);
+    mdb_segments_free(dev);
+    return rc;
 }
 
 } // namespace mdb
@@ -505,25 +558,7 @@ int mdb_agg_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const 
     if (!ctx || !inputs || !request || !inout) return fail("ctx, inputs, request and inout must not be NULL.");
     uint64_t n_cells = 0;
     if (bucket_request_check(request, &n_cells)) return 1;
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        if (!inputs[k]) return fail("A batch of the list is NULL.");
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    if (n == 0 || request->n_buckets == 0) return 0;
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    // (an upload the library holds, not its transient scratch: the batch then gets the cursor index a resident batch
-    // gets, and the host and device forms decode the same streams the same way - bit-identical results)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = buckets_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
-    mdb_segments_free(dev);
-    return rc;
+    return buckets_list_run(ctx, inputs, group_of_segment, n_inputs, request, n_cells, nullptr, inout);
 }
 
 int mdb_agg_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
@@ -531,6 +566,40 @@ int mdb_agg_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_
     if (!in) return fail("in must not be NULL.");
     const uint32_t *const groups[1] = {group_of_segment};
     return mdb_agg_buckets_list(ctx, &in, groups, 1, request, inout);
+}
+
+int mdb_agg_buckets_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                               const mdb_bucket_request *request, const mdb_value_filter *filter,
+                               mdb_agg_state *inout) {
+    if (!ctx || !in || !request || !filter || !inout)
+        return fail("ctx, in, request, filter and inout must not be NULL.");
+    uint64_t n_cells = 0;
+    ValueKeys keys;
+    mdb_bucket_request narrowed;
+    if (bucket_filter_check(request, filter, &n_cells, &keys, &narrowed)) return 1;
+    mdb::CallGuard lock(ctx);
+    MDB_HIP_CHECK(hipSetDevice(ctx->device));
+    return buckets_run(ctx, in, group_of_segment, &narrowed, n_cells, inout, nullptr, &keys);
+}
+
+int mdb_agg_buckets_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs,
+                                const uint32_t *const *group_of_segment, uint32_t n_inputs,
+                                const mdb_bucket_request *request, const mdb_value_filter *filter,
+                                mdb_agg_state *inout) {
+    if (!ctx || !inputs || !request || !filter || !inout)
+        return fail("ctx, inputs, request, filter and inout must not be NULL.");
+    uint64_t n_cells = 0;
+    ValueKeys keys;
+    mdb_bucket_request narrowed;
+    if (bucket_filter_check(request, filter, &n_cells, &keys, &narrowed)) return 1;
+    return buckets_list_run(ctx, inputs, group_of_segment, n_inputs, &narrowed, n_cells, &keys, inout);
+}
+
+int mdb_agg_buckets_filter(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                           const mdb_bucket_request *request, const mdb_value_filter *filter, mdb_agg_state *inout) {
+    if (!in) return fail("in must not be NULL.");
+    const uint32_t *const groups[1] = {group_of_segment};
+    return mdb_agg_buckets_filter_list(ctx, &in, groups, 1, request, filter, inout);
 }
 
 } // extern "C"

@@ -4205,14 +4205,16 @@ __global__ __launch_bounds__(256) void k_agg_bucket_piece_count(DevSegments s, B
                         ? b_last - b_first + 1 : 0;
 }
 
-// Writes the entries [e0, e1) of the call (entry e at e - e0).
+// Writes the entries [e0, e1) of the call (entry e at e - e0). Pred (AllValues, or the ValueKeys of
+// mdb_agg_buckets_filter*) says which decoded values are accumulated: the entries, and the decode, stay the same.
+template <typename Pred>
 __global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, BucketRequest r, const uint32_t *__restrict__ groups,
                                                                 const unsigned long long *__restrict__ piece_base,
                                                                 const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
                                                                 const unsigned long long *__restrict__ offsets,
                                                                 unsigned long long e0, unsigned long long e1,
                                                                 unsigned long long *__restrict__ keys,
-                                                                BucketPartial *__restrict__ out) {
+                                                                BucketPartial *__restrict__ out, Pred pred) {
     __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
     const int lane = threadIdx.x;
     const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
@@ -4270,7 +4272,7 @@ __global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, B
         const int64_t t = start + (int64_t)((uint64_t)(point_index + k) * (uint64_t)delta);
         const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
         while (bucket < b) flush();
-        acc.point(__uint_as_float(bits));
+        if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits));
     };
     reader.begin();
     reader.top_up(ring, lane);
@@ -4317,12 +4319,20 @@ int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest 
 
 int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
                           const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
-                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out) {
+                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
+                          const ValueKeys *filter) {
     const uint64_t n = index.n_pieces;
-    LaunchTimer timer(ctx, "k_agg_bucket_pieces");
-    hipLaunchKernelGGL(k_agg_bucket_pieces, dim3((uint32_t)((n + MDB_WAVE - 1) / MDB_WAVE)), dim3(MDB_WAVE), 0, ctx->stream, s,
-                       r, groups, piece_base, static_cast<const MvCursor *>(index.cursors), (unsigned long long)n, offsets,
-                       e0, e1, keys, out);
+    const dim3 blocks((uint32_t)((n + MDB_WAVE - 1) / MDB_WAVE));
+    const MvCursor *cursors = static_cast<const MvCursor *>(index.cursors);
+    if (filter) {
+        LaunchTimer timer(ctx, "k_agg_bucket_pieces_filter");
+        hipLaunchKernelGGL(k_agg_bucket_pieces<ValueKeys>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
+                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, *filter);
+    } else {
+        LaunchTimer timer(ctx, "k_agg_bucket_pieces");
+        hipLaunchKernelGGL(k_agg_bucket_pieces<AllValues>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
+                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, AllValues());
+    }
     return 0;
 }
 

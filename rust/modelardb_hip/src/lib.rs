@@ -327,6 +327,28 @@ fn grid_output(raw: *mut sys::mdb_grid_result, leftover_timestamps: &[i64], left
     }
 }
 
+/// `states` of a bucket call must hold exactly `n_groups * n_buckets` cells.
+fn check_bucket_cells(request: &BucketRequest, n_states: usize) -> Result<()> {
+    let cells = (request.n_groups as u64).checked_mul(request.n_buckets);
+    if cells != Some(n_states as u64) {
+        return Err(HipError(format!(
+            "states holds {} cells, the request n_groups * n_buckets = {} * {}",
+            n_states, request.n_groups, request.n_buckets
+        )));
+    }
+    Ok(())
+}
+
+/// Group ids of a bucket call: one per segment row, if given.
+fn check_group_ids(segments: &SegmentsView, group_of_segment: Option<&[u32]>) -> Result<()> {
+    if let Some(groups) = group_of_segment {
+        if groups.len() as u64 != segments.raw.n {
+            return Err(HipError(format!("{} group ids for {} segments", groups.len(), segments.raw.n)));
+        }
+    }
+    Ok(())
+}
+
 impl Context {
     /// Replaces the per-row `modelardb_compression::grid` loop of grid_exec.rs:323-356 for a whole
     /// batch: one upload of the segment columns, the kernels, one copy of the reconstructed columns
@@ -450,22 +472,58 @@ impl Context {
         request: &BucketRequest,
         states: &mut [AggState],
     ) -> Result<()> {
-        let cells = (request.n_groups as u64).checked_mul(request.n_buckets);
-        if cells != Some(states.len() as u64) {
-            return Err(HipError(format!(
-                "states holds {} cells, the request n_groups * n_buckets = {} * {}",
-                states.len(),
-                request.n_groups,
-                request.n_buckets
-            )));
-        }
-        if let Some(groups) = group_of_segment {
-            if groups.len() as u64 != segments.raw.n {
-                return Err(HipError(format!("{} group ids for {} segments", groups.len(), segments.raw.n)));
-            }
-        }
+        check_bucket_cells(request, states.len())?;
+        check_group_ids(segments, group_of_segment)?;
         let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
         check(unsafe { sys::mdb_agg_buckets(self.raw(), &segments.raw, groups, request, states.as_mut_ptr()) })
+    }
+
+    /// [`Context::agg_buckets`] of the points that pass `filter` (its time range ANDed with the request's): replaces
+    /// GridExec -> FilterExec -> AggregateExec under `GROUP BY <tags>, date_bin(...)`. A cell without a passing
+    /// point stays as it was.
+    pub fn agg_buckets_filter(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        filter: &ValueFilter,
+        states: &mut [AggState],
+    ) -> Result<()> {
+        check_bucket_cells(request, states.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe {
+            sys::mdb_agg_buckets_filter(self.raw(), &segments.raw, groups, request, filter, states.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::agg_buckets_filter`] for several batches at once (rows in the order of the slice), folded as one
+    /// batch. `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn agg_buckets_filter_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        filter: &ValueFilter,
+        states: &mut [AggState],
+    ) -> Result<()> {
+        check_bucket_cells(request, states.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_agg_buckets_filter_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                             request, filter, states.as_mut_ptr())
+        })
     }
 
     /// Replaces the body of `try_compress_univariate_time_series` after its two argument checks

@@ -300,6 +300,16 @@ unsafe extern "C" {
                                      inout: *mut mdb_agg_state) -> c_int;
     pub fn mdb_agg_batch_range_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments, n_inputs: u32,
                                     t_lo: i64, t_hi: i64, which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets_filter(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                  request: *const mdb_bucket_request, filter: *const mdb_value_filter,
+                                  inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets_filter_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                      request: *const mdb_bucket_request, filter: *const mdb_value_filter,
+                                      inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_buckets_filter_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                       group_of_segment: *const *const u32, n_inputs: u32,
+                                       request: *const mdb_bucket_request, filter: *const mdb_value_filter,
+                                       inout: *mut mdb_agg_state) -> c_int;
 
     // ---- fit (replaces try_compress_univariate_time_series, compression.rs:191-275) -----------------
     pub fn mdb_compress_series(ctx: *mut mdb_ctx, ts: *const i64, values: *const f32, n: u64,
