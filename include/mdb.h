@@ -323,6 +323,65 @@ int mdb_agg_buckets_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs,
                                 const mdb_bucket_request *request, const mdb_value_filter *filter,
                                 mdb_agg_state *inout);
 
+/* Extension: row masks - a predicate on one field column selects the rows of another:
+ *   SELECT AVG(active_power) FROM turbine WHERE wind_speed > 12.0 AND rotor_speed <= 14.5 AND ts BETWEEN ...
+ * which the reference answers with GridExec per field -> SortedJoinExec -> FilterExec (-> AggregateExec): every point of
+ * every named field is rebuilt, zipped by row position (query/sorted_join_exec.rs:278-310) and a BooleanArray per
+ * predicate decides the rows. Here that bitmap is made from one field's segments and consumed by another's without a
+ * point of either being materialised.
+ *   The mask: over n_rows rows, ceil(n_rows / 64) uint64_t words in device memory; row r is bit r % 64 of word r / 64
+ *     (on a little-endian host byte for byte an Arrow boolean bitmap, bit r % 8 of byte r / 8: a downloaded mask wraps
+ *     as a BooleanBuffer as it is). Bits at and beyond n_rows in the last word are zero after every call that writes a
+ *     mask. The rows are those of mdb_grid_batch_range(in, t_lo, t_hi), in that order.
+ *   Row alignment: two field batches line up when they hold the same series in the same order with the same
+ *     timestamps; row r of one is then the same data point's row in the other, however differently the two were cut
+ *     into segments, under any common time range. The consuming calls check the row COUNT only, as the reference does -
+ *     but where SortedJoinExec truncates to its shortest input (sorted_join_exec.rs:252-273, a workaround for
+ *     half-transferred folders) these calls fail, before writing anything, with a message that names both counts.
+ *   Errors (mdb_last_error set, outputs untouched): as stated per call, and the error classes of the range calls. */
+#define MDB_MASK_AND 0u
+#define MDB_MASK_OR 1u
+#define MDB_MASK_XOR 2u
+#define MDB_MASK_ANDNOT 3u /* a & ~b */
+#define MDB_MASK_NOT 4u    /* ~a; b must be NULL */
+/* The mask of `filter` over the rows of mdb_grid_batch_range_dev(in, filter->t_lo, filter->t_hi): a bit is set iff the
+ * row's value passes the value bounds in totalOrder (exactly the rows mdb_grid_batch_filter_dev keeps). *n_rows: the
+ * number of rows; *n_set (may be NULL): the set bits. Every word the mask owns is written (the buffer need not be
+ * cleared). Errors: cap_words below ceil(n_rows / 64), unknown filter flags or reserved != 0. */
+int mdb_mask_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, uint64_t *mask,
+                        uint64_t cap_words, uint64_t *n_rows, uint64_t *n_set);
+/* out = a op b (MDB_MASK_*) over n_rows rows; out may be a or b. The padding bits stay zero (NOT clears the tail).
+ * *n_set (may be NULL): the set bits of out. Errors: an unknown op, b != NULL with MDB_MASK_NOT, a NULL mask. */
+int mdb_mask_combine_dev(mdb_ctx *ctx, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t *out, uint64_t n_rows,
+                         uint64_t *n_set);
+/* The rows of mdb_grid_batch_range_dev(in, t_lo, t_hi) whose bit is set, in order. out_ts may be NULL (values only: the
+ * second and later fields of a join). out_rows_per_segment and metrics as for mdb_grid_batch_filter_dev (the row
+ * counters count the rows produced, the segment counters are the range call's). The number of rows produced is the
+ * mask's n_set. Errors: the batch does not have exactly n_rows rows under [t_lo, t_hi]; cap too small. */
+int mdb_grid_batch_mask_dev(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const uint64_t *mask,
+                            uint64_t n_rows, int64_t *out_ts, float *out_val, uint32_t *out_rows_per_segment, uint64_t cap,
+                            uint64_t *n_out, mdb_grid_metrics *metrics);
+/* The selected points folded into *inout (a host pointer, as for mdb_agg_batch_range_dev) with the rules of
+ * mdb_agg_batch_filter: COUNT / MIN / MAX exact, SUM the f64 sum of the selected f32 points within the 0.001 % of the
+ * other aggregates; no selected point leaves *inout as mdb_agg_batch_range leaves it. A fixed reduction tree, no float
+ * atomics: two runs agree bit for bit. Errors: the batch does not have exactly n_rows rows under [t_lo, t_hi]. */
+int mdb_agg_batch_mask_dev(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const uint64_t *mask,
+                           uint64_t n_rows, uint32_t which_mask, mdb_agg_state *inout);
+/* One-call forms for host callers: pred_fields[k] is a host batch and filters[k] its predicate; the predicates are
+ * ANDed. The time range of the call is the INTERSECTION of all filters' [t_lo, t_hi], applied to every predicate field
+ * and to `target` so that the rows line up (an empty intersection selects nothing). target may be one of the predicate
+ * batches (the same pointer): it is then uploaded once. Every batch is uploaded once, the masks live in the context's
+ * scratch, only the result crosses PCIe. n_preds == 0: mdb_agg_batch_range over the whole time axis / every row.
+ * The results agree bit for bit with the _dev calls above on the same batches.
+ * Errors: a predicate field whose row count under the range differs from the target's; those of the _dev calls. */
+int mdb_agg_batch_where(mdb_ctx *ctx, const mdb_segments *const *pred_fields, const mdb_value_filter *filters,
+                        uint32_t n_preds, const mdb_segments *target, uint32_t which_mask, mdb_agg_state *inout);
+/* The same for rows, into a page-locked mdb_grid_result as mdb_grid_batch_filter_owned (reserve_front, freed by
+ * mdb_grid_result_free). flags: MDB_GRID_VALUES_ONLY (result->timestamps is NULL) or 0; anything else is an error. */
+int mdb_grid_batch_where_owned(mdb_ctx *ctx, const mdb_segments *const *pred_fields, const mdb_value_filter *filters,
+                               uint32_t n_preds, const mdb_segments *target, uint32_t flags, uint64_t reserve_front,
+                               mdb_grid_result **out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -36,6 +36,16 @@ MDB_VALUE_HI_OPEN = 2
 MDB_VALUE_NO_LO = 4
 MDB_VALUE_NO_HI = 8
 
+# mdb_mask_combine_dev operations (mdb.h)
+MDB_MASK_AND = 0
+MDB_MASK_OR = 1
+MDB_MASK_XOR = 2
+MDB_MASK_ANDNOT = 3
+MDB_MASK_NOT = 4
+
+MDB_GRID_HAS_RANGE = 1
+MDB_GRID_VALUES_ONLY = 2
+
 F32_MAX = 3.4028234663852886e38
 
 
@@ -259,6 +269,20 @@ _HIP_SYMBOLS = {
     "mdb_agg_buckets_filter_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
                                               C.c_uint32, C.POINTER(BucketRequestC), C.POINTER(ValueFilterC),
                                               C.c_void_p]),
+    "mdb_mask_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_void_p, C.c_uint64,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mdb_mask_combine_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.POINTER(C.c_uint64)]),
+    "mdb_grid_batch_mask_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_int64, C.c_int64, C.c_void_p, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                          C.POINTER(GridMetricsC)]),
+    "mdb_agg_batch_mask_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_int64, C.c_int64, C.c_void_p, C.c_uint64,
+                                         C.c_uint32, C.POINTER(AggStateC)]),
+    "mdb_agg_batch_where": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(ValueFilterC), C.c_uint32,
+                                      C.POINTER(SegmentsC), C.c_uint32, C.POINTER(AggStateC)]),
+    "mdb_grid_batch_where_owned": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(ValueFilterC),
+                                             C.c_uint32, C.POINTER(SegmentsC), C.c_uint32, C.c_uint64,
+                                             C.POINTER(C.POINTER(GridResultC))]),
     "mdb_compress_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, ErrorBoundC,
                                       C.POINTER(C.POINTER(SegmentsOwnedC))]),
     "mdb_compress_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

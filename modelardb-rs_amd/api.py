@@ -217,6 +217,17 @@ def value_filter_bits(flt):
         struct.unpack_from("<I", raw, _abi.ValueFilterC.v_hi.offset)[0]
 
 
+def unpack_mask(raw, n_rows):
+    """The bytes of a row mask (little-endian words: an Arrow boolean bitmap) as a bool array of n_rows entries."""
+    raw = np.ascontiguousarray(raw).view(np.uint8)
+    return np.unpackbits(raw, bitorder="little")[: int(n_rows)].astype(bool)
+
+
+def mask_words(n_rows):
+    """64-bit words of a row mask over n_rows rows (mdb.h: row r is bit r % 64 of word r / 64)."""
+    return (int(n_rows) + 63) // 64
+
+
 def is_value_within_error_bound(eb, real_value, approximate_value):
     """models/mod.rs:53-77 through the C ABI (host arithmetic, no GPU)."""
     lib = _abi.load_hip_library()
@@ -591,6 +602,119 @@ class Context:
         self._check(self.lib.mdb_agg_batch_filter_dev(self.handle, C.byref(dev_segments.seg), C.byref(flt), which_mask,
                                                       C.byref(state)))
         return state
+
+    # ---- row masks: a predicate on one field selects the rows of another (mdb_mask_*, mdb_*_mask*, mdb_*_where*) ----
+
+    def mask_filter_dev(self, dev_segments, flt, mask_ptr, cap_words, want_set=True):
+        """mdb_mask_filter_dev: the mask of `flt` over the rows of the batch under the filter's time range, into
+        `cap_words` device words at mask_ptr. Returns (n_rows, n_set) (n_set None unless want_set)."""
+        n_rows, n_set = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mdb_mask_filter_dev(self.handle, C.byref(dev_segments.seg), C.byref(flt), C.c_void_p(mask_ptr),
+                                                 int(cap_words), C.byref(n_rows), C.byref(n_set) if want_set else None))
+        return n_rows.value, (n_set.value if want_set else None)
+
+    def mask_combine_dev(self, op, a_ptr, b_ptr, out_ptr, n_rows):
+        """mdb_mask_combine_dev: out = a op b (MDB_MASK_*; b_ptr None for NOT); returns the set bits of out."""
+        n_set = C.c_uint64()
+        self._check(self.lib.mdb_mask_combine_dev(self.handle, int(op), C.c_void_p(a_ptr), C.c_void_p(b_ptr),
+                                                  C.c_void_p(out_ptr), int(n_rows), C.byref(n_set)))
+        return n_set.value
+
+    def upload_mask(self, bits):
+        """A bool array as a device mask (the padding bits zero); returns the pointer (dev_free it)."""
+        bits = np.ascontiguousarray(bits, dtype=bool)
+        packed = np.zeros(max(mask_words(len(bits)), 1) * 8, dtype=np.uint8)
+        packed[: (len(bits) + 7) // 8] = np.packbits(bits, bitorder="little")
+        return self.upload_array(packed)
+
+    def download_mask(self, pointer, n_rows, with_padding=False):
+        """A device mask as a bool array of n_rows entries (with_padding: of all 64 * words bits, padding included)."""
+        words = mask_words(n_rows)
+        if words == 0:
+            return np.zeros(0, dtype=bool)
+        raw = self.download_array(pointer, words * 8, np.uint8)
+        return unpack_mask(raw, words * 64 if with_padding else n_rows)
+
+    def grid_mask_dev(self, dev_segments, t_lo, t_hi, mask_ptr, n_rows, out_ts_ptr, out_val_ptr, cap, rows_ptr=None):
+        """mdb_grid_batch_mask_dev into device columns (out_ts_ptr None: values only); returns (rows produced, metrics)."""
+        n_out = C.c_uint64()
+        metrics = _abi.GridMetricsC()
+        self._check(self.lib.mdb_grid_batch_mask_dev(
+            self.handle, C.byref(dev_segments.seg), int(t_lo), int(t_hi), C.c_void_p(mask_ptr), int(n_rows),
+            C.c_void_p(out_ts_ptr), C.c_void_p(out_val_ptr), C.c_void_p(rows_ptr), int(cap), C.byref(n_out), C.byref(metrics)))
+        return n_out.value, metrics.as_dict()
+
+    def grid_mask_resident(self, dev_segments, t_lo, t_hi, mask_ptr, n_rows, n_set, values_only=False):
+        """The dev form on a resident batch, downloaded: (timestamps or None, values, rows_per_segment, metrics).
+        n_set: the set bits of the mask (the size of the output)."""
+        out_ts = None if values_only else self.dev_alloc(8 * max(n_set, 1))
+        out_val = self.dev_alloc(4 * max(n_set, 1))
+        rows = self.dev_alloc(4 * max(len(dev_segments), 1))
+        try:
+            produced, metrics = self.grid_mask_dev(dev_segments, t_lo, t_hi, mask_ptr, n_rows, out_ts, out_val, n_set, rows)
+            assert produced == n_set
+            return (None if values_only else self.download_array(out_ts, n_set, np.int64),
+                    self.download_array(out_val, n_set, np.float32),
+                    self.download_array(rows, len(dev_segments), np.uint32), metrics)
+        finally:
+            for pointer in (out_ts, out_val, rows):
+                if pointer is not None:
+                    self.dev_free(pointer)
+
+    def agg_mask_dev(self, dev_segments, t_lo, t_hi, mask_ptr, n_rows, which_mask, state=None):
+        """mdb_agg_batch_mask_dev: the points the mask selects folded into `state`."""
+        state = state or _abi.AggStateC.fresh()
+        self._check(self.lib.mdb_agg_batch_mask_dev(self.handle, C.byref(dev_segments.seg), int(t_lo), int(t_hi),
+                                                    C.c_void_p(mask_ptr), int(n_rows), which_mask, C.byref(state)))
+        return state
+
+    @staticmethod
+    def _where_arguments(pred_batches, filters):
+        if len(pred_batches) != len(filters):
+            raise ValueError("one filter per predicate batch")
+        views = {}
+        for batch in pred_batches:  # (the same batch twice: the same mdb_segments pointer)
+            if id(batch) not in views:
+                views[id(batch)] = batch.as_c()
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(pred_batches), 1))(
+            *[C.pointer(views[id(batch)]) for batch in pred_batches])
+        array = (_abi.ValueFilterC * max(len(filters), 1))(*filters)
+        return views, pointers, array
+
+    def agg_where(self, pred_batches, filters, target, which_mask, state=None):
+        """mdb_agg_batch_where: agg(target) WHERE filters[0](pred_batches[0]) AND ... over host batches."""
+        views, pointers, array = self._where_arguments(pred_batches, filters)
+        target_view = views.get(id(target)) or target.as_c()
+        state = state or _abi.AggStateC.fresh()
+        self._check(self.lib.mdb_agg_batch_where(self.handle, pointers, array, len(filters), C.byref(target_view),
+                                                 which_mask, C.byref(state)))
+        return state
+
+    def grid_where(self, pred_batches, filters, target, values_only=False, reserve_front=0, flags=None):
+        """mdb_grid_batch_where_owned: the rows of target WHERE ...; copies (timestamps or None, values,
+        rows_per_segment, metrics)."""
+        views, pointers, array = self._where_arguments(pred_batches, filters)
+        target_view = views.get(id(target)) or target.as_c()
+        if flags is None:
+            flags = _abi.MDB_GRID_VALUES_ONLY if values_only else 0
+        out = C.POINTER(_abi.GridResultC)()
+        self._check(self.lib.mdb_grid_batch_where_owned(self.handle, pointers, array, len(filters), C.byref(target_view),
+                                                        int(flags), int(reserve_front), C.byref(out)))
+        try:
+            result = out.contents
+            n, n_segments = int(result.n), int(result.n_segments)
+
+            def copy_of(pointer, count, dtype):
+                if count == 0:
+                    return np.zeros(0, dtype=dtype)
+                buffer = (C.c_char * (count * np.dtype(dtype).itemsize)).from_address(pointer)
+                return np.frombuffer(buffer, dtype=dtype).copy()
+
+            return (copy_of(result.timestamps, n, np.int64) if result.timestamps else None,
+                    copy_of(result.values, n, np.float32), copy_of(result.rows_per_segment, n_segments, np.uint32),
+                    result.metrics.as_dict())
+        finally:
+            self.lib.mdb_grid_result_free(out)
 
     # ---- aggregates per time bucket ----------------------------------------------------------------
 

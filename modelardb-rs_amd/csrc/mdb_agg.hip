@@ -13,6 +13,7 @@
 // deterministic; it differs from the reference's sequential f64 accumulation only in rounding order.
 // Algorithmic bytes: COUNT 32 B/segment, MIN 4, MAX 4, SUM/AVG 73 B/segment + payloads.
 #include "mdb_agg_dev.hpp"
+#include "mdb_mask.hpp"
 #include "mdb_segment_dev.hpp"
 
 #include <cfloat>
@@ -358,8 +359,35 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_filter(DevSegments s, int64
                    static_cast<TsWalkRange *>(nullptr), keys, lds);
 }
 
-int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const ValueKeys &keys,
-                   uint32_t which_mask, mdb_agg_state *inout) {
+// The masked aggregates (mdb_agg_batch_mask_dev, mdb_agg_batch_where): k_agg_filter's loop with a predicate on the ROW
+// of a point (segment_rows, mdb_mask.hpp): segment i's first point inside the range is row first_row[i] of the mask.
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_mask(DevSegments s, int64_t t_lo, int64_t t_hi,
+                                                          const unsigned long long *__restrict__ first_row, RowBits bits,
+                                                          AggPartial *__restrict__ partials) {
+    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+    AggPartial p = empty_partial();
+    for (uint64_t i = (uint64_t)blockIdx.x * AGG_THREADS + threadIdx.x; i < s.n; i += (uint64_t)gridDim.x * AGG_THREADS) {
+        if (s.end_time[i] < t_lo || s.start_time[i] > t_hi) continue;
+        const SegInfo info = analyse_segment(s, i);
+        uint32_t error = info.error;
+        if (!error) {
+            RangeAcc acc;
+            segment_rows(s, i, info, t_lo, t_hi, first_row[i], bits, acc, &error);
+            p.sum += acc.sum;
+            p.count += acc.count;
+            p.min = min_num(p.min, acc.min);
+            p.max = max_num(p.max, acc.max);
+        }
+        p.error |= error;
+    }
+    block_reduce(p, lds);
+    if (threadIdx.x == 0) partials[blockIdx.x] = p;
+}
+
+// One partial per workgroup (written by `launch(n_blocks, partials)`) through k_agg_finish, folded into the caller's
+// state exactly as agg_run folds a range's.
+template <typename Launch>
+static int agg_selected_run(mdb_ctx *ctx, const mdb_segments *in, uint32_t which_mask, mdb_agg_state *inout, Launch launch) {
     if (in->n == 0) return 0; // (as agg_run: an empty batch leaves the state as it is)
     AggPartial host = empty_partial_host();
     {
@@ -368,11 +396,7 @@ int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t
         if (scratch_reserve(ctx, SCRATCH_AGG_PARTIALS, (uint64_t)(n_blocks + 1) * sizeof(AggPartial), &p)) return 1;
         AggPartial *partials = static_cast<AggPartial *>(p);
         AggPartial *result = partials + n_blocks;
-        {
-            LaunchTimer timer(ctx, "k_agg_filter");
-            hipLaunchKernelGGL(k_agg_filter, dim3(n_blocks), dim3(AGG_THREADS), 0, ctx->stream, to_dev(in), t_lo, t_hi,
-                               keys, partials);
-        }
+        launch(n_blocks, partials);
         {
             LaunchTimer timer(ctx, "k_agg_finish");
             hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials, n_blocks, result);
@@ -382,7 +406,6 @@ int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t
         MDB_HIP_CHECK(hipGetLastError());
         if (host.error) return fail(describe_error(host.error));
     }
-    // Folded into the caller's state exactly as agg_run folds a range's.
     if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) inout->count += host.count;
     if (which_mask & MDB_AGG_MIN) inout->min = (inout->min != inout->min) ? host.min
                                                : (host.min < inout->min ? host.min : inout->min);
@@ -390,6 +413,24 @@ int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t
                                                : (host.max > inout->max ? host.max : inout->max);
     if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) inout->sum += host.sum;
     return 0;
+}
+
+int agg_filter_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const ValueKeys &keys,
+                   uint32_t which_mask, mdb_agg_state *inout) {
+    return agg_selected_run(ctx, in, which_mask, inout, [&](uint32_t n_blocks, AggPartial *partials) {
+        LaunchTimer timer(ctx, "k_agg_filter");
+        hipLaunchKernelGGL(k_agg_filter, dim3(n_blocks), dim3(AGG_THREADS), 0, ctx->stream, to_dev(in), t_lo, t_hi, keys,
+                           partials);
+    });
+}
+
+int agg_mask_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const unsigned long long *first_row,
+                 const unsigned long long *words, uint64_t n_words, uint32_t which_mask, mdb_agg_state *inout) {
+    return agg_selected_run(ctx, in, which_mask, inout, [&](uint32_t n_blocks, AggPartial *partials) {
+        LaunchTimer timer(ctx, "k_agg_mask");
+        hipLaunchKernelGGL(k_agg_mask, dim3(n_blocks), dim3(AGG_THREADS), 0, ctx->stream, to_dev(in), t_lo, t_hi,
+                           first_row, RowBits{words, n_words}, partials);
+    });
 }
 
 int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int64_t t_hi,

@@ -92,6 +92,8 @@ enum ScratchSlot {
     SCRATCH_FILTER_SEGMENTS, // mdb_grid_*_filter*: per segment its interval, row count, offsets and the scans
     SCRATCH_FILTER_GATHER,   // ... the columns of the segments whose points are tested one by one
     SCRATCH_FILTER_SLICE,    // ... one slice of their rebuilt points
+    SCRATCH_MASK_SEGMENTS,   // mdb_mask_* / mdb_*_mask*: per segment its rows, first row, class, counts and the scans
+    SCRATCH_MASK_WORDS,      // ... the masks of the host forms (mdb_*_where*)
     SCRATCH_SLOT_COUNT
 };
 

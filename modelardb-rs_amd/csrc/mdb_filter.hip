@@ -28,6 +28,7 @@
 // closed forms over the interval of a PMC-Mean / Swing model part, a test per point in its decoders.
 #include "mdb_agg_dev.hpp"
 #include "mdb_filter.hpp"
+#include "mdb_filter_points.hpp"
 #include "mdb_host_side.hpp"
 #include "mdb_scan.hpp"
 
@@ -39,21 +40,9 @@
 
 namespace mdb {
 
-constexpr int FILTER_THREADS = 256;
 constexpr uint64_t FILTER_SLICE_DEFAULT = 1ull << 24; // points per slice of the per-point segments: 192 MB of rows
 
-// An interval segment's passing model points: n points from timestamp `start` on, `delta` apart.
-struct FilterRun {
-    int64_t start;
-    int64_t delta;
-    double slope;
-    double intercept;
-    float value;
-    uint32_t type;
-    uint32_t n;
-    uint32_t pad;
-};
-static_assert(sizeof(FilterRun) == 48, "48 B per segment");
+// (FilterRun, classify_segment, Gathered, FilterPass: mdb_filter_points.hpp - shared with the row masks)
 
 // counts[i]: the passing model points of segment i's interval (its final row count once k_filter_points has added
 // the per-point ones). per_point[i]: 0 - no point of segment i is tested one by one; 1 + m - its rows in the range
@@ -64,41 +53,9 @@ __global__ __launch_bounds__(FILTER_THREADS) void k_filter_classify(DevSegments 
                                                                     uint32_t *__restrict__ per_point) {
     const uint64_t i = (uint64_t)blockIdx.x * FILTER_THREADS + threadIdx.x;
     if (i >= s.n) return;
-    FilterRun r{0, 0, 0.0, 0.0, 0.0f, 0u, 0u, 0u};
-    uint32_t tested = 0;
-    // (the range grid takes no point of a segment outside the range; its errors are grid_range_plan's to report)
-    if (!(s.end_time[i] < t_lo || s.start_time[i] > t_hi)) {
-        const SegInfo info = analyse_segment(s, i);
-        const SegDesc &d = info.desc;
-        const uint32_t type = d.flags & FLAG_TYPE_MASK;
-        uint32_t k_lo = 0, k_hi = 0;
-        if (info.error) {
-        } else if (!(d.flags & FLAG_REGULAR) || type == MDB_MACAQUE_V_ID) {
-            tested = 1;
-        } else if (regular_index_interval(d.start, d.delta, d.n_total, t_lo, t_hi, &k_lo, &k_hi)) {
-            uint32_t model_rows = 0;
-            bool whole = false;
-            if (k_lo < d.n_model) {
-                const uint32_t a = k_lo, b = min(k_hi, d.n_model - 1);
-                model_rows = b - a + 1;
-                uint32_t ra = a, rb = b;
-                const int run = model_run(d, type, a, b, keys, &ra, &rb);
-                if (run == RUN_POINTS) {
-                    whole = true;
-                } else if (run == RUN_INTERVAL) {
-                    r.start = d.start + (int64_t)((uint64_t)ra * (uint64_t)d.delta);
-                    r.delta = d.delta;
-                    r.slope = d.slope;
-                    r.intercept = d.intercept;
-                    r.value = d.value;
-                    r.type = type;
-                    r.n = rb - ra + 1;
-                }
-            }
-            if (whole) tested = 1;
-            else if (d.n_total > d.n_model && k_hi >= d.n_model) tested = 1 + model_rows;
-        }
-    }
+    FilterRun r;
+    uint32_t tested = 0, run_first = 0;
+    classify_segment(s, i, t_lo, t_hi, keys, &r, &tested, &run_first);
     runs[i] = r;
     counts[i] = r.n;
     per_point[i] = tested;
@@ -111,21 +68,6 @@ struct FilterTested { // (scan functor: the segments with points tested one by o
 struct FilterRows { // (scan functor: rows per segment)
     const uint32_t *rows;
     __device__ uint64_t operator()(uint64_t i) const { return rows[i]; }
-};
-
-// The columns of the per-point segments, in segment order, with the same payload buffers.
-struct Gathered {
-    int8_t *type;
-    int64_t *start;
-    int64_t *end;
-    float *min;
-    float *max;
-    uint4 *ts_views;
-    uint4 *value_views;
-    uint4 *residual_views;
-    uint32_t *origin;    // the segment of the batch
-    uint32_t *skip;      // rows of the range grid the interval has decided
-    uint32_t *rows;      // rows of the range grid
 };
 
 __global__ __launch_bounds__(FILTER_THREADS) void k_filter_gather(DevSegments s, const uint32_t *__restrict__ per_point,
@@ -232,38 +174,16 @@ uint64_t slice_points(const mdb_ctx *ctx) {
     return points;
 }
 
-// One filtered grid call over a batch in HBM: what the count leaves for the write.
-struct FilterPass {
-    const mdb_segments *in = nullptr;
-    int64_t t_lo = 0, t_hi = 0;
-    ValueKeys keys{INT32_MAX, INT32_MIN};
-    uint64_t total = 0;            // rows produced
-    mdb_grid_metrics metrics{};
-    FilterRun *runs = nullptr;
-    uint32_t *counts = nullptr;    // rows per segment
-    unsigned long long *offsets = nullptr;
-    // the per-point segments
-    uint64_t n_tested = 0;
-    mdb_segments tested{};         // their batch (the gathered columns)
-    Gathered g{};
-    std::vector<std::pair<uint64_t, uint64_t>> slices; // [j0, j1) of the gathered segments
-    uint64_t slice_cap = 0;
-    int64_t *slice_ts = nullptr;
-    float *slice_val = nullptr;
-    uint32_t *slice_rows = nullptr;
-    unsigned long long *slice_first = nullptr;
-    unsigned long long *slice_block_sums = nullptr;
-    bool kept = false;             // one slice, still in place from the count
-};
-
 int fold_filter(const mdb_value_filter *filter, ValueKeys *keys) {
     if (!value_keys_fold(*filter, keys))
         return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
     return 0;
 }
 
+} // namespace
+
 // The range grid of gathered segments [j0, j1) into the slice buffers, and the first row of each.
-int rebuild_slice(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1) {
+int filter_rebuild_slice(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1) {
     mdb_segments part = f.tested;
     part.n = j1 - j0;
     part.model_type_id = f.tested.model_type_id + j0;
@@ -282,55 +202,19 @@ int rebuild_slice(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1) {
                                  "k_filter_scan");
 }
 
-void launch_points(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1, bool write, int64_t *out_ts, float *out_val) {
-    const uint64_t n = j1 - j0;
-    if (n == 0) return;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS / MDB_WAVE - 1) / (FILTER_THREADS / MDB_WAVE), 8192);
-    LaunchTimer timer(ctx, write ? "k_filter_points_write" : "k_filter_points_count");
-    if (write)
-        hipLaunchKernelGGL(k_filter_points<true>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
-                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
-    else
-        hipLaunchKernelGGL(k_filter_points<false>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
-                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
-}
-
-// Pass 1: classify, count the per-point segments' passing rows (slice by slice), scan. Sets f.total and f.metrics.
-int filter_count(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, FilterPass &f) {
-    f.in = in;
-    f.t_lo = filter->t_lo;
-    f.t_hi = filter->t_hi;
-    if (fold_filter(filter, &f.keys)) return 1;
-    // The range grid's prepass: its segment counters and its verdict on the segments.
-    uint64_t range_total = 0;
-    if (grid_range_plan(ctx, in, f.t_lo, f.t_hi, &range_total, &f.metrics, nullptr)) return 1;
+// The per-point segments of f.in (per_point[i] != 0) gathered, their slices planned, the slice buffers reserved.
+int filter_gather_tested(mdb_ctx *ctx, FilterPass &f, const uint32_t *per_point, unsigned long long *position,
+                         unsigned long long *block_sums) {
+    const mdb_segments *in = f.in;
     const uint64_t n = in->n;
-    if (n == 0) return 0;
-    if (n > 0xffffffffull) return fail("Too many segments for one filtered call.");
     const DevSegments s = to_dev(in);
-    const uint64_t runs_bytes = align_up(n * sizeof(FilterRun), 256), words_bytes = align_up(n * 4, 256);
-    const uint64_t offsets_bytes = align_up((n + 1) * 8, 256), sums_bytes = align_up(scan_block_sums_bytes(n), 256);
-    void *p = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_FILTER_SEGMENTS, runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes + 256, &p))
-        return 1;
-    uint8_t *base = static_cast<uint8_t *>(p);
-    f.runs = reinterpret_cast<FilterRun *>(base);
-    f.counts = reinterpret_cast<uint32_t *>(base + runs_bytes);
-    uint32_t *per_point = reinterpret_cast<uint32_t *>(base + runs_bytes + words_bytes);
-    f.offsets = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes);
-    unsigned long long *position = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + offsets_bytes);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes);
-    unsigned long long *by_type = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes);
     const uint32_t blocks = (uint32_t)((n + FILTER_THREADS - 1) / FILTER_THREADS);
-    {
-        LaunchTimer timer(ctx, "k_filter_classify");
-        hipLaunchKernelGGL(k_filter_classify, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, s, f.t_lo, f.t_hi,
-                           f.keys, f.runs, f.counts, per_point);
-    }
+    void *p = nullptr;
     if (device_exclusive_scan(ctx, FilterTested{per_point}, n, position, block_sums, "k_filter_scan")) return 1;
     MDB_HIP_CHECK(hipMemcpyAsync(&f.n_tested, position + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (f.n_tested > 0) {
+    if (f.n_tested == 0) return 0;
+    {
         const uint64_t m = f.n_tested;
         const uint64_t b8 = align_up(m * 8, 256), b4 = align_up(m * 4, 256), b16 = align_up(m * 16, 256), b1 = align_up(m, 256);
         if (scratch_reserve(ctx, SCRATCH_FILTER_GATHER, b1 + 2 * b8 + 5 * b4 + 3 * b16, &p)) return 1;
@@ -401,19 +285,77 @@ int filter_count(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *f
         f.slice_rows = reinterpret_cast<uint32_t *>(slice + sts + sval);
         f.slice_first = reinterpret_cast<unsigned long long *>(slice + sts + sval + srows);
         f.slice_block_sums = reinterpret_cast<unsigned long long *>(slice + sts + sval + srows + sfirst);
+    }
+    return 0;
+}
+
+int filter_rows_by_type(mdb_ctx *ctx, const int8_t *types, const uint32_t *counts, uint64_t n,
+                        unsigned long long *by_type) {
+    MDB_HIP_CHECK(hipMemsetAsync(by_type, 0, 3 * 8, ctx->stream));
+    if (n == 0) return 0;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS - 1) / FILTER_THREADS, 1024);
+    LaunchTimer timer(ctx, "k_filter_rows_by_type");
+    hipLaunchKernelGGL(k_filter_rows_by_type, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, types, counts, n, by_type);
+    return 0;
+}
+
+namespace {
+
+void launch_points(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1, bool write, int64_t *out_ts, float *out_val) {
+    const uint64_t n = j1 - j0;
+    if (n == 0) return;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS / MDB_WAVE - 1) / (FILTER_THREADS / MDB_WAVE), 8192);
+    LaunchTimer timer(ctx, write ? "k_filter_points_write" : "k_filter_points_count");
+    if (write)
+        hipLaunchKernelGGL(k_filter_points<true>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
+                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
+    else
+        hipLaunchKernelGGL(k_filter_points<false>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
+                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
+}
+
+// Pass 1: classify, count the per-point segments' passing rows (slice by slice), scan. Sets f.total and f.metrics.
+int filter_count(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, FilterPass &f) {
+    f.in = in;
+    f.t_lo = filter->t_lo;
+    f.t_hi = filter->t_hi;
+    if (fold_filter(filter, &f.keys)) return 1;
+    // The range grid's prepass: its segment counters and its verdict on the segments.
+    uint64_t range_total = 0;
+    if (grid_range_plan(ctx, in, f.t_lo, f.t_hi, &range_total, &f.metrics, nullptr)) return 1;
+    const uint64_t n = in->n;
+    if (n == 0) return 0;
+    if (n > 0xffffffffull) return fail("Too many segments for one filtered call.");
+    const DevSegments s = to_dev(in);
+    const uint64_t runs_bytes = align_up(n * sizeof(FilterRun), 256), words_bytes = align_up(n * 4, 256);
+    const uint64_t offsets_bytes = align_up((n + 1) * 8, 256), sums_bytes = align_up(scan_block_sums_bytes(n), 256);
+    void *p = nullptr;
+    if (scratch_reserve(ctx, SCRATCH_FILTER_SEGMENTS, runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes + 256, &p))
+        return 1;
+    uint8_t *base = static_cast<uint8_t *>(p);
+    f.runs = reinterpret_cast<FilterRun *>(base);
+    f.counts = reinterpret_cast<uint32_t *>(base + runs_bytes);
+    uint32_t *per_point = reinterpret_cast<uint32_t *>(base + runs_bytes + words_bytes);
+    f.offsets = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes);
+    unsigned long long *position = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + offsets_bytes);
+    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes);
+    unsigned long long *by_type = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes);
+    const uint32_t blocks = (uint32_t)((n + FILTER_THREADS - 1) / FILTER_THREADS);
+    {
+        LaunchTimer timer(ctx, "k_filter_classify");
+        hipLaunchKernelGGL(k_filter_classify, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, s, f.t_lo, f.t_hi,
+                           f.keys, f.runs, f.counts, per_point);
+    }
+    if (filter_gather_tested(ctx, f, per_point, position, block_sums)) return 1;
+    if (f.n_tested > 0) {
         for (const auto &range : f.slices) {
-            if (rebuild_slice(ctx, f, range.first, range.second)) return 1;
+            if (filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
             launch_points(ctx, f, range.first, range.second, false, nullptr, nullptr);
         }
         f.kept = f.slices.size() == 1;
     }
     if (device_exclusive_scan(ctx, FilterRows{f.counts}, n, f.offsets, block_sums, "k_filter_scan")) return 1;
-    MDB_HIP_CHECK(hipMemsetAsync(by_type, 0, 3 * 8, ctx->stream));
-    {
-        LaunchTimer timer(ctx, "k_filter_rows_by_type");
-        hipLaunchKernelGGL(k_filter_rows_by_type, dim3(std::min<uint32_t>(blocks, 1024)), dim3(FILTER_THREADS), 0,
-                           ctx->stream, in->model_type_id, f.counts, n, by_type);
-    }
+    if (filter_rows_by_type(ctx, in->model_type_id, f.counts, n, by_type)) return 1;
     unsigned long long words[4] = {0, 0, 0, 0};
     MDB_HIP_CHECK(hipMemcpyAsync(&words[0], f.offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     MDB_HIP_CHECK(hipMemcpyAsync(&words[1], by_type, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -437,7 +379,7 @@ int filter_write(mdb_ctx *ctx, FilterPass &f, int64_t *out_ts, float *out_val, u
                                f.offsets, out_ts, out_val);
         }
         for (const auto &range : f.slices) {
-            if (!f.kept && rebuild_slice(ctx, f, range.first, range.second)) return 1;
+            if (!f.kept && filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
             launch_points(ctx, f, range.first, range.second, true, out_ts, out_val);
         }
     }

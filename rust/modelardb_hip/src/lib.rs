@@ -26,7 +26,7 @@ use std::sync::Arc;
 use arrow::array::{
     Array, ArrayRef, BinaryViewArray, Float32Array, Int8Array, Int16Array, StringViewArray,
 };
-use arrow::buffer::{Buffer, ScalarBuffer};
+use arrow::buffer::{BooleanBuffer, Buffer, ScalarBuffer};
 use arrow::datatypes::Schema;
 use arrow::record_batch::RecordBatch;
 use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
@@ -36,6 +36,7 @@ pub use sys::{
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
+pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
 pub use sys::{MDB_AGG_AVG, MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM};
 
 /// Failure reported by the library (the text of `mdb_last_error()`).
@@ -417,6 +418,82 @@ impl Context {
         check(unsafe {
             sys::mdb_agg_batch_filter_list(self.raw(), inputs.as_ptr(), inputs.len() as u32, filter, which_mask, state)
         })
+    }
+
+    /// `agg(target) WHERE filters[0](pred_fields[0]) AND filters[1](pred_fields[1]) ...` (`mdb_agg_batch_where`):
+    /// replaces GridExec per field -> SortedJoinExec -> FilterExec -> AggregateExec when every conjunct of the
+    /// FilterExec compares ONE field column (or the timestamp) with literals. The time range of the call is the
+    /// intersection of the filters' ranges; the field batches must line up (the same series in the same order with
+    /// the same timestamps - the fields of one time series table do). `target` may be one of `pred_fields`.
+    pub fn agg_where(
+        &self,
+        pred_fields: &[&SegmentsView],
+        filters: &[ValueFilter],
+        target: &SegmentsView,
+        which_mask: u32,
+        state: &mut AggState,
+    ) -> Result<()> {
+        assert_eq!(pred_fields.len(), filters.len());
+        let inputs: Vec<*const sys::mdb_segments> = pred_fields.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_agg_batch_where(self.raw(), inputs.as_ptr(), filters.as_ptr(), inputs.len() as u32, &target.raw,
+                                     which_mask, state)
+        })
+    }
+
+    /// The rows of `target` under the same conjunction (`mdb_grid_batch_where_owned`), timestamps and values: what
+    /// the first field column of the join contributes. Only the selected rows cross PCIe.
+    pub fn grid_where_owned(
+        &self,
+        pred_fields: &[&SegmentsView],
+        filters: &[ValueFilter],
+        target: &SegmentsView,
+        leftover_timestamps: &[i64],
+        leftover_values: &[f32],
+    ) -> Result<GridOutput> {
+        assert_eq!(pred_fields.len(), filters.len());
+        assert_eq!(leftover_timestamps.len(), leftover_values.len());
+        let inputs: Vec<*const sys::mdb_segments> = pred_fields.iter().map(|view| &view.raw as *const _).collect();
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::mdb_grid_batch_where_owned(self.raw(), inputs.as_ptr(), filters.as_ptr(), inputs.len() as u32,
+                                            &target.raw, 0, leftover_timestamps.len() as u64, &mut raw)
+        })?;
+        Ok(grid_output(raw, leftover_timestamps, leftover_values))
+    }
+
+    /// The same with `MDB_GRID_VALUES_ONLY`: the values of the selected rows alone, for the second and later field
+    /// columns of the join (sorted_join_exec.rs:268-275 takes the timestamps from the first input).
+    pub fn grid_where_values_owned(
+        &self,
+        pred_fields: &[&SegmentsView],
+        filters: &[ValueFilter],
+        target: &SegmentsView,
+    ) -> Result<(ValueArray, Vec<u32>)> {
+        assert_eq!(pred_fields.len(), filters.len());
+        let inputs: Vec<*const sys::mdb_segments> = pred_fields.iter().map(|view| &view.raw as *const _).collect();
+        let mut raw = ptr::null_mut();
+        check(unsafe {
+            sys::mdb_grid_batch_where_owned(self.raw(), inputs.as_ptr(), filters.as_ptr(), inputs.len() as u32,
+                                            &target.raw, sys::MDB_GRID_VALUES_ONLY, 0, &mut raw)
+        })?;
+        let block = Arc::new(GridBlock(NonNull::new(raw).expect("success with a null result")));
+        let result = unsafe { block.0.as_ref() };
+        let total = result.n as usize;
+        let rows_per_segment =
+            unsafe { std::slice::from_raw_parts(result.rows_per_segment, result.n_segments as usize) }.to_vec();
+        let values = unsafe {
+            Buffer::from_custom_allocation(NonNull::new_unchecked(result.values.cast::<u8>()), 4 * total, block.clone())
+        };
+        Ok((ValueArray::new(ScalarBuffer::new(values, 0, total), None), rows_per_segment))
+    }
+
+    /// Device memory for a row mask over `n_rows` rows (`ceil(n_rows / 64)` words, not cleared: every call that
+    /// writes a mask writes all of its words).
+    pub fn row_mask(&self, n_rows: u64) -> Result<RowMask<'_>> {
+        let mut words = ptr::null_mut();
+        check(unsafe { sys::mdb_dev_alloc(self.raw(), n_rows.div_ceil(64).max(1) * 8, &mut words) })?;
+        Ok(RowMask { context: self, words: words.cast(), n_rows, cap_words: n_rows.div_ceil(64).max(1) })
     }
 
     /// Replaces the per-row `len` / `sum` loops of the accumulators: folds the batch into `state`
@@ -863,6 +940,67 @@ impl GridTicket {
             segments: result.n_segments,
             rows_created: result.n,
         })
+    }
+}
+
+/// A row-selection bitmap in device memory (include/mdb.h, "row masks"): row `r` is bit `r % 64` of word `r / 64`,
+/// the bits at and beyond `n_rows` are zero - byte for byte an Arrow boolean bitmap. Made by [`Context::row_mask`],
+/// filled and consumed by the `mdb_*_dev` calls on batches that are resident on the device (through
+/// [`RowMask::as_ptr`] / [`RowMask::as_mut_ptr`]); freed on drop.
+pub struct RowMask<'a> {
+    context: &'a Context,
+    words: *mut u64,
+    n_rows: u64,
+    cap_words: u64,
+}
+
+impl RowMask<'_> {
+    pub fn n_rows(&self) -> u64 {
+        self.n_rows
+    }
+
+    pub fn cap_words(&self) -> u64 {
+        self.cap_words
+    }
+
+    pub fn as_ptr(&self) -> *const u64 {
+        self.words
+    }
+
+    pub fn as_mut_ptr(&mut self) -> *mut u64 {
+        self.words
+    }
+
+    /// `self = self op other` (`MDB_MASK_AND` / `OR` / `XOR` / `ANDNOT`), or `self = !self` (`MDB_MASK_NOT`, `other`
+    /// None); returns the number of set bits.
+    pub fn combine(&mut self, op: u32, other: Option<&RowMask>) -> Result<u64> {
+        if let Some(other) = other {
+            if other.n_rows != self.n_rows {
+                return Err(HipError(format!("masks over {} and {} rows", self.n_rows, other.n_rows)));
+            }
+        }
+        let mut n_set = 0u64;
+        check(unsafe {
+            sys::mdb_mask_combine_dev(self.context.raw(), op, self.words, other.map_or(ptr::null(), |mask| mask.words),
+                                      self.words, self.n_rows, &mut n_set)
+        })?;
+        Ok(n_set)
+    }
+
+    /// The mask on the host, as the `BooleanBuffer` a `BooleanArray` is made of (no bit is touched on the way).
+    pub fn download(&self) -> Result<BooleanBuffer> {
+        let mut words = vec![0u64; self.n_rows.div_ceil(64) as usize];
+        check(unsafe {
+            sys::mdb_dev_download(self.context.raw(), words.as_mut_ptr().cast(), self.words.cast_const().cast(),
+                                  8 * words.len() as u64)
+        })?;
+        Ok(BooleanBuffer::new(Buffer::from_vec(words), 0, self.n_rows as usize))
+    }
+}
+
+impl Drop for RowMask<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::mdb_dev_free(self.context.raw(), self.words.cast()) };
     }
 }
 

@@ -181,6 +181,13 @@ pub struct mdb_bucket_request {
     pub which_mask: u32,
 }
 
+/// Operations of `mdb_mask_combine_dev` on row masks (`out = a op b`; `MDB_MASK_NOT`: `~a`, `b` must be null).
+pub const MDB_MASK_AND: u32 = 0;
+pub const MDB_MASK_OR: u32 = 1;
+pub const MDB_MASK_XOR: u32 = 2;
+pub const MDB_MASK_ANDNOT: u32 = 3;
+pub const MDB_MASK_NOT: u32 = 4;
+
 /// `mdb_value_filter` flags: an open lower / upper end, or none at all.
 pub const MDB_VALUE_LO_OPEN: u32 = 1;
 pub const MDB_VALUE_HI_OPEN: u32 = 2;
@@ -310,6 +317,23 @@ unsafe extern "C" {
                                        group_of_segment: *const *const u32, n_inputs: u32,
                                        request: *const mdb_bucket_request, filter: *const mdb_value_filter,
                                        inout: *mut mdb_agg_state) -> c_int;
+    // ---- row masks: a predicate on one field column selects the rows of another (include/mdb.h) ----
+    pub fn mdb_mask_filter_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, filter: *const mdb_value_filter,
+                               mask: *mut u64, cap_words: u64, n_rows: *mut u64, n_set: *mut u64) -> c_int;
+    pub fn mdb_mask_combine_dev(ctx: *mut mdb_ctx, op: u32, a: *const u64, b: *const u64, out: *mut u64, n_rows: u64,
+                                n_set: *mut u64) -> c_int;
+    pub fn mdb_grid_batch_mask_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64,
+                                   mask: *const u64, n_rows: u64, out_ts: *mut i64, out_val: *mut f32,
+                                   out_rows_per_segment: *mut u32, cap: u64, n_out: *mut u64,
+                                   metrics: *mut mdb_grid_metrics) -> c_int;
+    pub fn mdb_agg_batch_mask_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64,
+                                  mask: *const u64, n_rows: u64, which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_agg_batch_where(ctx: *mut mdb_ctx, pred_fields: *const *const mdb_segments,
+                               filters: *const mdb_value_filter, n_preds: u32, target: *const mdb_segments,
+                               which_mask: u32, inout: *mut mdb_agg_state) -> c_int;
+    pub fn mdb_grid_batch_where_owned(ctx: *mut mdb_ctx, pred_fields: *const *const mdb_segments,
+                                      filters: *const mdb_value_filter, n_preds: u32, target: *const mdb_segments,
+                                      flags: u32, reserve_front: u64, out: *mut *mut mdb_grid_result) -> c_int;
 
     // ---- fit (replaces try_compress_univariate_time_series, compression.rs:191-275) -----------------
     pub fn mdb_compress_series(ctx: *mut mdb_ctx, ts: *const i64, values: *const f32, n: u64,
