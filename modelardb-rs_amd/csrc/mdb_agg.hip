@@ -12,6 +12,10 @@
 // k_agg_finish reduces the partials with one workgroup. The fixed tree makes SUM run-to-run
 // deterministic; it differs from the reference's sequential f64 accumulation only in rounding order.
 // Algorithmic bytes: COUNT 32 B/segment, MIN 4, MAX 4, SUM/AVG 73 B/segment + payloads.
+// k_agg_range, k_agg_filter, k_agg_mask: one loop (agg_range_body) over the segments that reach into a time range,
+// 1 thread / segment through segment_range (mdb_agg_dev.hpp) with the selector of the call - every point, the points
+// whose value passes, the points whose row is set in a mask - into the same tree. Every pass ends in agg_finish
+// (k_agg_finish, the read-back, the streams' error) and every call in agg_fold; the four host forms are agg_host_run.
 #include "mdb_agg_dev.hpp"
 #include "mdb_mask.hpp"
 #include "mdb_segment_dev.hpp"
@@ -257,8 +261,9 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_finish(const AggPartial *__
 // that reach into the range, len() and - PMC-Mean / Swing without residuals - the aggregates of their points inside
 // it, as the walk of their streams has found them (ts_walk_for_aggregates; the same values in the same order as
 // segment_range's own pass over such a segment).
-// (the body of k_agg_range and of k_agg_filter: `pred` says which values count - every value for the range calls)
-template <typename Pred>
+// (the body of k_agg_range, k_agg_filter and k_agg_mask: `selector_of(i)` is segment i's selector - which of its points
+// count, mdb_filter.hpp; the same for every segment but for a mask, whose selector holds the segment's first row)
+template <typename SelectorOf>
 __device__ __forceinline__ void agg_range_body(DevSegments s, int64_t t_lo, int64_t t_hi, uint32_t mode,
                                                uint32_t mv_min_values,
                                                AggPartial *__restrict__ partials,
@@ -267,8 +272,8 @@ __device__ __forceinline__ void agg_range_body(DevSegments s, int64_t t_lo, int6
                                                const unsigned int *__restrict__ walked_error,
                                                const unsigned long long *__restrict__ indexed_piece_base,
                                                const TsWalkRange *__restrict__ whole_in,
-                                               TsWalkRange *__restrict__ whole_out, const Pred &pred,
-                                               AggPartial *lds) {
+                                               TsWalkRange *__restrict__ whole_out,
+                                               const SelectorOf &selector_of, AggPartial *lds) {
     AggPartial p = empty_partial();
     if (walked_error && blockIdx.x == 0 && threadIdx.x == 0) p.error |= *walked_error;
     const TimeRange range = {t_lo, t_hi, 1};
@@ -319,7 +324,7 @@ __device__ __forceinline__ void agg_range_body(DevSegments s, int64_t t_lo, int6
                 acc.min = walked.min;
                 acc.max = walked.max;
             } else {
-                segment_range(s, i, info, t_lo, t_hi, acc, &error, tail_by_pieces, pred);
+                segment_range(s, i, info, t_lo, t_hi, acc, &error, tail_by_pieces, selector_of(i));
             }
             p.sum += acc.sum;
             p.count += acc.count;
@@ -344,74 +349,85 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_range(DevSegments s, int64_
                                                            TsWalkRange *__restrict__ whole_out) {
     __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
     agg_range_body(s, t_lo, t_hi, mode, mv_min_values, partials, walked_totals, walked_ranges, walked_error,
-                   indexed_piece_base, whole_in, whole_out, AllValues(), lds);
+                   indexed_piece_base, whole_in, whole_out, [](uint64_t) { return AllValues(); }, lds);
 }
 
-// The filtered aggregates (mdb_agg_batch_filter*): k_agg_range's loop with a value predicate, every segment that
-// reaches into the range worked out by its own lane (no walks, cursors or deferred streams: segment_range decodes
-// the streams it needs), partials into the same fixed tree.
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_filter(DevSegments s, int64_t t_lo, int64_t t_hi, ValueKeys keys,
-                                                            AggPartial *__restrict__ partials) {
-    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+// The filtered and the masked aggregates: k_agg_range's loop with a selector, every segment that reaches into the range
+// worked out by its own lane (no walks, cursors or deferred streams: segment_range decodes the streams it needs),
+// partials into the same fixed tree.
+template <typename SelectorOf>
+__device__ __forceinline__ void agg_selected_body(const DevSegments &s, int64_t t_lo, int64_t t_hi,
+                                                  AggPartial *__restrict__ partials, const SelectorOf &selector_of,
+                                                  AggPartial *lds) {
     agg_range_body(s, t_lo, t_hi, AGG_SUM_ALL, 0xffffffffu, partials, static_cast<const uint32_t *>(nullptr),
                    static_cast<const TsWalkRange *>(nullptr), static_cast<const unsigned int *>(nullptr),
                    static_cast<const unsigned long long *>(nullptr), static_cast<const TsWalkRange *>(nullptr),
-                   static_cast<TsWalkRange *>(nullptr), keys, lds);
+                   static_cast<TsWalkRange *>(nullptr), selector_of, lds);
 }
 
-// The masked aggregates (mdb_agg_batch_mask_dev, mdb_agg_batch_where): k_agg_filter's loop with a predicate on the ROW
-// of a point (segment_rows, mdb_mask.hpp): segment i's first point inside the range is row first_row[i] of the mask.
+// mdb_agg_batch_filter*: a value predicate.
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_filter(DevSegments s, int64_t t_lo, int64_t t_hi, ValueKeys keys,
+                                                            AggPartial *__restrict__ partials) {
+    __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
+    agg_selected_body(s, t_lo, t_hi, partials, [&](uint64_t) { return keys; }, lds);
+}
+
+// mdb_agg_batch_mask_dev, mdb_agg_batch_where: a predicate on the ROW of a point (SegmentRows, mdb_mask.hpp): segment
+// i's first point inside the range is row first_row[i] of the mask.
 __global__ __launch_bounds__(AGG_THREADS) void k_agg_mask(DevSegments s, int64_t t_lo, int64_t t_hi,
                                                           const unsigned long long *__restrict__ first_row, RowBits bits,
                                                           AggPartial *__restrict__ partials) {
     __shared__ AggPartial lds[AGG_THREADS / MDB_WAVE];
-    AggPartial p = empty_partial();
-    for (uint64_t i = (uint64_t)blockIdx.x * AGG_THREADS + threadIdx.x; i < s.n; i += (uint64_t)gridDim.x * AGG_THREADS) {
-        if (s.end_time[i] < t_lo || s.start_time[i] > t_hi) continue;
-        const SegInfo info = analyse_segment(s, i);
-        uint32_t error = info.error;
-        if (!error) {
-            RangeAcc acc;
-            segment_rows(s, i, info, t_lo, t_hi, first_row[i], bits, acc, &error);
-            p.sum += acc.sum;
-            p.count += acc.count;
-            p.min = min_num(p.min, acc.min);
-            p.max = max_num(p.max, acc.max);
-        }
-        p.error |= error;
-    }
-    block_reduce(p, lds);
-    if (threadIdx.x == 0) partials[blockIdx.x] = p;
+    agg_selected_body(s, t_lo, t_hi, partials, [&](uint64_t i) { return SegmentRows{bits, first_row[i]}; }, lds);
 }
 
-// One partial per workgroup (written by `launch(n_blocks, partials)`) through k_agg_finish, folded into the caller's
-// state exactly as agg_run folds a range's.
-template <typename Launch>
-static int agg_selected_run(mdb_ctx *ctx, const mdb_segments *in, uint32_t which_mask, mdb_agg_state *inout, Launch launch) {
-    if (in->n == 0) return 0; // (as agg_run: an empty batch leaves the state as it is)
-    AggPartial host = empty_partial_host();
+// One partial per workgroup of a pass over the n segments of a batch, and behind them k_agg_finish's result.
+static int agg_partials(mdb_ctx *ctx, uint64_t n, uint32_t *n_blocks, AggPartial **partials) {
+    *n_blocks = (uint32_t)std::min<uint64_t>((n + AGG_THREADS - 1) / AGG_THREADS, 256 * 8); // grid-stride beyond 8 workgroups per CU
+    void *p;
+    if (scratch_reserve(ctx, SCRATCH_AGG_PARTIALS, (uint64_t)(*n_blocks + 1) * sizeof(AggPartial), &p)) return 1;
+    *partials = static_cast<AggPartial *>(p);
+    return 0;
+}
+
+// The partials of a pass through k_agg_finish and back to the host (one synchronisation). A fault the kernels found
+// in the streams fails with its message (and is in host->error, which is 0 on every other way out).
+static int agg_finish(mdb_ctx *ctx, AggPartial *partials, uint32_t n_blocks, AggPartial *host) {
+    *host = empty_partial_host();
+    AggPartial *result = partials + n_blocks;
     {
-        const uint32_t n_blocks = (uint32_t)std::min<uint64_t>((in->n + AGG_THREADS - 1) / AGG_THREADS, 256 * 8);
-        void *p;
-        if (scratch_reserve(ctx, SCRATCH_AGG_PARTIALS, (uint64_t)(n_blocks + 1) * sizeof(AggPartial), &p)) return 1;
-        AggPartial *partials = static_cast<AggPartial *>(p);
-        AggPartial *result = partials + n_blocks;
-        launch(n_blocks, partials);
-        {
-            LaunchTimer timer(ctx, "k_agg_finish");
-            hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials, n_blocks, result);
-        }
-        MDB_HIP_CHECK(hipMemcpyAsync(&host, result, sizeof(AggPartial), hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (host.error) return fail(describe_error(host.error));
+        LaunchTimer timer(ctx, "k_agg_finish");
+        hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials, n_blocks, result);
     }
+    AggPartial back;
+    MDB_HIP_CHECK(hipMemcpyAsync(&back, result, sizeof(AggPartial), hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    *host = back;
+    if (host->error) return fail(describe_error(host->error));
+    return 0;
+}
+
+// A batch's aggregates folded into the caller's running state exactly as update_batch would continue it.
+static void agg_fold(const AggPartial &host, uint32_t which_mask, mdb_agg_state *inout) {
     if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) inout->count += host.count;
     if (which_mask & MDB_AGG_MIN) inout->min = (inout->min != inout->min) ? host.min
                                                : (host.min < inout->min ? host.min : inout->min);
     if (which_mask & MDB_AGG_MAX) inout->max = (inout->max != inout->max) ? host.max
                                                : (host.max > inout->max ? host.max : inout->max);
     if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) inout->sum += host.sum;
+}
+
+// One partial per workgroup (written by `launch(n_blocks, partials)`) finished and folded as agg_run does a range's.
+template <typename Launch>
+static int agg_selected_run(mdb_ctx *ctx, const mdb_segments *in, uint32_t which_mask, mdb_agg_state *inout, Launch launch) {
+    if (in->n == 0) return 0; // (as agg_run: an empty batch leaves the state as it is)
+    uint32_t n_blocks = 0;
+    AggPartial *partials = nullptr, host;
+    if (agg_partials(ctx, in->n, &n_blocks, &partials)) return 1;
+    launch(n_blocks, partials);
+    if (agg_finish(ctx, partials, n_blocks, &host)) return 1;
+    agg_fold(host, which_mask, inout);
     return 0;
 }
 
@@ -436,14 +452,9 @@ int agg_mask_run(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_h
 int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int64_t t_hi,
             uint32_t which_mask, mdb_agg_state *inout) {
     if (in->n == 0) return 0;
-    const uint32_t max_blocks = 256 * 8; // grid-stride beyond 8 workgroups per CU
-    const uint32_t n_blocks =
-        (uint32_t)std::min<uint64_t>((in->n + AGG_THREADS - 1) / AGG_THREADS, max_blocks);
-    void *p;
-    if (scratch_reserve(ctx, SCRATCH_AGG_PARTIALS, (uint64_t)(n_blocks + 1) * sizeof(AggPartial), &p))
-        return 1;
-    AggPartial *partials = static_cast<AggPartial *>(p);
-    AggPartial *result = partials + n_blocks;
+    uint32_t n_blocks = 0;
+    AggPartial *partials = nullptr;
+    if (agg_partials(ctx, in->n, &n_blocks, &partials)) return 1;
     DevSegments s = to_dev(in);
     const bool sums_wanted = !range && (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG));
     bool mv_forced = false;
@@ -535,11 +546,9 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
                                        static_cast<const TsWalkRange *>(kept->range_whole), static_cast<const unsigned int *>(nullptr),
                                        indexed_piece_base, static_cast<const TsWalkRange *>(nullptr),
                                        static_cast<TsWalkRange *>(fresh));
-                    hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials, n_blocks, result);
                 }
                 AggPartial made;
-                MDB_HIP_CHECK(hipMemcpyAsync(&made, result, sizeof(AggPartial), hipMemcpyDeviceToHost, ctx->stream));
-                MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                if (agg_finish(ctx, partials, n_blocks, &made) && !made.error) return 1;
                 if (made.error) { // (a fault in the streams: every call finds and reports it itself; not tried again for this kind)
                     kept->range_acc_failed[slot] = true;
                 } else {
@@ -586,22 +595,13 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
                            which_mask, sums_wanted && !stream_sums ? AGG_SUM_DEFER : AGG_SUM_ALL, mv_min_values, partials,
                            walked_totals, walked_sums, walked_error, stream_sums, only_with_pieces);
     }
-    {
-        LaunchTimer timer(ctx, "k_agg_finish");
-        hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials,
-                           n_blocks, result);
-    }
     AggPartial host;
-    MDB_HIP_CHECK(hipMemcpyAsync(&host, result, sizeof(AggPartial), hipMemcpyDeviceToHost,
-                                 ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    if (keep_walk && !host.error) {
+    if (agg_finish(ctx, partials, n_blocks, &host)) return 1;
+    if (keep_walk) { // (no fault in the streams)
         std::lock_guard<std::mutex> lock(resident->mutex);
         resident->agg_walk_built = true;
         if (walked_sums || !walked_totals) resident->agg_walk_with_sums = true;
     }
-    if (host.error) return fail(describe_error(host.error));
     if (host.deferred > 0) {
         // Long MacaqueV streams were left aside for the decoders of mdb_grid.hip ...
         bool handled = false;
@@ -626,17 +626,8 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
                                    static_cast<const unsigned int *>(nullptr), static_cast<const float *>(nullptr),
                                    static_cast<const unsigned long long *>(nullptr));
             }
-            {
-                LaunchTimer timer(ctx, "k_agg_finish");
-                hipLaunchKernelGGL(k_agg_finish, dim3(1), dim3(AGG_THREADS), 0, ctx->stream, partials,
-                                   n_blocks, result);
-            }
             AggPartial late;
-            MDB_HIP_CHECK(hipMemcpyAsync(&late, result, sizeof(AggPartial), hipMemcpyDeviceToHost,
-                                         ctx->stream));
-            MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            MDB_HIP_CHECK(hipGetLastError());
-            if (late.error) return fail(describe_error(late.error));
+            if (agg_finish(ctx, partials, n_blocks, &late)) return 1;
             totals.sum = late.sum;
             totals.count = late.count;
             totals.min = late.min;
@@ -657,13 +648,7 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
         host.min = by_pieces.min < host.min ? by_pieces.min : host.min;
         host.max = by_pieces.max > host.max ? by_pieces.max : host.max;
     }
-    // Fold into the caller's running state exactly as update_batch would continue it.
-    if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) inout->count += host.count;
-    if (which_mask & MDB_AGG_MIN) inout->min = (inout->min != inout->min) ? host.min
-                                               : (host.min < inout->min ? host.min : inout->min);
-    if (which_mask & MDB_AGG_MAX) inout->max = (inout->max != inout->max) ? host.max
-                                               : (host.max > inout->max ? host.max : inout->max);
-    if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) inout->sum += host.sum;
+    agg_fold(host, which_mask, inout);
     return 0;
 }
 
@@ -683,6 +668,35 @@ struct HostWalk {
     }
     ~HostWalk() { finish(); }
 };
+
+// The host forms of the plain aggregates: a list of host batches (a single batch: a list of one - the upload and the
+// index of one batch ARE those of such a list) under an optional time range, as one device batch through agg_run.
+// SUM decodes every value of a MacaqueV stream: the long ones piece by piece from cursors that host threads leave
+// while the batch is staged and crosses PCIe (mdb_grid.hip, mv_host_index; HostWalk) - under a range, into the
+// streams that reach into it.
+int agg_host_run(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs, const MvHostRange *range,
+                 uint32_t which_mask, mdb_agg_state *inout) {
+    if (n_inputs == 0) return 0;
+    for (uint32_t k = 0; k < n_inputs; k++)
+        if (!inputs[k]) return fail("A batch of the list is NULL.");
+    MvCallIndex index;
+    HostWalk walk;
+    // (without a range only SUM / AVG read a value; under one COUNT alone reads none, MIN / MAX / SUM of a segment the
+    // range cuts do)
+    const uint32_t reads_values = range ? ~(uint32_t)MDB_AGG_COUNT : (uint32_t)(MDB_AGG_SUM | MDB_AGG_AVG);
+    if ((which_mask & reads_values) != 0 && mv_host_index_worthwhile(inputs, n_inputs))
+        walk.start([&index, inputs, n_inputs, range] { mv_host_index(inputs, n_inputs, &index.piece_base, &index.cursors, range); });
+    mdb::CallGuard lock(ctx);
+    MDB_HIP_CHECK(hipSetDevice(ctx->device));
+    mdb_segments_owned *dev = nullptr;
+    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
+    walk.finish();
+    int rc = mv_call_index_use(ctx, dev->seg, index);
+    if (!rc) rc = agg_run(ctx, &dev->seg, range != nullptr, range ? range->lo : 0, range ? range->hi : 0, which_mask, inout);
+    mv_call_index_done();
+    mdb_segments_free(dev);
+    return rc;
+}
 } // namespace
 
 extern "C" {
@@ -705,93 +719,27 @@ int mdb_agg_batch_range_dev(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, 
 
 int mdb_agg_batch(mdb_ctx *ctx, const mdb_segments *in, uint32_t which_mask, mdb_agg_state *inout) {
     if (!ctx || !in || !inout) return fail("ctx, in and inout must not be NULL.");
-    // SUM decodes every value of a MacaqueV stream: the long ones piece by piece from cursors that host threads
-    // leave while the batch is on its way (mdb_grid.hip, mv_host_index).
-    // (they walk while the batch is staged and crosses PCIe: HostWalk)
-    MvCallIndex index;
-    HostWalk walk;
-    if ((which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) && mv_host_index_worthwhile(&in, 1))
-        walk.start([&index, in] { mv_call_index_build(in, &index); });
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segments_locked(ctx, in, true, &dev)) return 1;
-    walk.finish();
-    int rc = mv_call_index_use(ctx, dev->seg, index);
-    if (!rc) rc = agg_run(ctx, &dev->seg, false, 0, 0, which_mask, inout);
-    mv_call_index_done();
-    mdb_segments_free(dev);
-    return rc;
+    return agg_host_run(ctx, &in, 1, nullptr, which_mask, inout);
 }
 
 int mdb_agg_batch_list(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs, uint32_t which_mask,
                        mdb_agg_state *inout) {
     if (!ctx || !inputs || !inout) return fail("ctx, inputs and inout must not be NULL.");
-    if (n_inputs == 0) return 0;
-    for (uint32_t k = 0; k < n_inputs; k++)
-        if (!inputs[k]) return fail("A batch of the list is NULL.");
-    MvCallIndex index;
-    HostWalk walk;
-    if ((which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) && mv_host_index_worthwhile(inputs, n_inputs))
-        walk.start([&index, inputs, n_inputs] { mv_host_index(inputs, n_inputs, &index.piece_base, &index.cursors); });
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
-    walk.finish();
-    int rc = mv_call_index_use(ctx, dev->seg, index);
-    if (!rc) rc = agg_run(ctx, &dev->seg, false, 0, 0, which_mask, inout);
-    mv_call_index_done();
-    mdb_segments_free(dev);
-    return rc;
+    return agg_host_run(ctx, inputs, n_inputs, nullptr, which_mask, inout);
 }
 
 int mdb_agg_batch_range(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi,
                         uint32_t which_mask, mdb_agg_state *inout) {
     if (!ctx || !in || !inout) return fail("ctx, in and inout must not be NULL.");
-    // (cursors into the long MacaqueV streams that reach into the range, by host threads: see mdb_agg_batch)
-    MvCallIndex index;
-    const MvHostRange host_range{t_lo, t_hi};
-    HostWalk walk;
-    // (COUNT alone reads no value; MIN / MAX / SUM of a segment the range cuts do)
-    if ((which_mask & ~(uint32_t)MDB_AGG_COUNT) != 0 && mv_host_index_worthwhile(&in, 1))
-        walk.start([&index, in, &host_range] { mv_call_index_build(in, &index, &host_range); });
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segments_locked(ctx, in, true, &dev)) return 1;
-    walk.finish();
-    int rc = mv_call_index_use(ctx, dev->seg, index);
-    if (!rc) rc = agg_run(ctx, &dev->seg, true, t_lo, t_hi, which_mask, inout);
-    mv_call_index_done();
-    mdb_segments_free(dev);
-    return rc;
+    const MvHostRange range{t_lo, t_hi};
+    return agg_host_run(ctx, &in, 1, &range, which_mask, inout);
 }
 
 int mdb_agg_batch_range_list(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs, int64_t t_lo,
                              int64_t t_hi, uint32_t which_mask, mdb_agg_state *inout) {
     if (!ctx || !inputs || !inout) return fail("ctx, inputs and inout must not be NULL.");
-    if (n_inputs == 0) return 0;
-    for (uint32_t k = 0; k < n_inputs; k++)
-        if (!inputs[k]) return fail("A batch of the list is NULL.");
-    // (the list form of mdb_agg_batch_range: cursors into the long MacaqueV streams that reach into the range)
-    MvCallIndex index;
-    const MvHostRange host_range{t_lo, t_hi};
-    HostWalk walk;
-    if ((which_mask & ~(uint32_t)MDB_AGG_COUNT) != 0 && mv_host_index_worthwhile(inputs, n_inputs))
-        walk.start([&index, inputs, n_inputs, &host_range] {
-            mv_host_index(inputs, n_inputs, &index.piece_base, &index.cursors, &host_range);
-        });
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
-    walk.finish();
-    int rc = mv_call_index_use(ctx, dev->seg, index);
-    if (!rc) rc = agg_run(ctx, &dev->seg, true, t_lo, t_hi, which_mask, inout);
-    mv_call_index_done();
-    mdb_segments_free(dev);
-    return rc;
+    const MvHostRange range{t_lo, t_hi};
+    return agg_host_run(ctx, inputs, n_inputs, &range, which_mask, inout);
 }
 
 } // extern "C"

@@ -1,6 +1,7 @@
-// mdb_agg_dev.hpp - the points of one segment inside a time range, aggregated without materialising them:
-// shared by the time-range aggregates (mdb_agg.hip, k_agg_range) and the bucketed ones (mdb_buckets.hip, and their
-// MacaqueV pieces in mdb_grid.hip).
+// mdb_agg_dev.hpp - the points of one segment inside a time range, aggregated without materialising them
+// (segment_range: ONE walk of a segment's model and streams, with a selector that says which points count - every one,
+// by value, or by row): shared by the time-range, filtered and masked aggregates (mdb_agg.hip: k_agg_range,
+// k_agg_filter, k_agg_mask) and the bucketed ones (mdb_buckets.hip, and their MacaqueV pieces in mdb_grid.hip).
 #pragma once
 
 #include "mdb_filter.hpp"
@@ -71,14 +72,35 @@ __device__ __forceinline__ void model_closed_form(const SegDesc &d, uint32_t typ
     }
 }
 
-// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi] (and whose value passes `pred`: every
-// value for the range calls; a ValueKeys for the filtered ones, mdb_filter.hpp).
-// tail_by_pieces: the residual tail's points are k_agg_mv_range's (regular timestamps only).
-template <typename Pred = AllValues>
+// What the two selectors of mdb_filter.hpp make of the model points [a, b]: all of them in closed form, or ...
+__device__ __forceinline__ void AllValues::model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t,
+                                                 RangeAcc &acc) const {
+    model_closed_form(d, type, a, b, acc);
+}
+// ... the passing ones: none, one interval in closed form, or (an end is NaN) one by one.
+__device__ __forceinline__ void ValueKeys::model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t,
+                                                 RangeAcc &acc) const {
+    uint32_t ra = a, rb = b;
+    const int run = model_run(d, type, a, b, *this, &ra, &rb);
+    if (run == RUN_INTERVAL) {
+        model_closed_form(d, type, ra, rb, acc);
+    } else if (run == RUN_POINTS) {
+        for (uint32_t k = a; k <= b; k++) {
+            const float v = model_value_at(d, type, d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta));
+            if (pass(v)) acc.point(v);
+        }
+    }
+}
+
+// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi] and which `sel` selects (mdb_filter.hpp:
+// every one for the range calls, by value for the filtered ones; mdb_mask.hpp: by row for the masked ones). The row
+// of a point is its position among the segment's points inside the range.
+// tail_by_pieces: the residual tail's points are k_agg_mv_range's (regular timestamps only; never with rows).
+template <typename Sel = AllValues>
 __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, const SegInfo &info,
                                               int64_t t_lo, int64_t t_hi, RangeAcc &acc,
                                               uint32_t *error, bool tail_by_pieces = false,
-                                              const Pred &pred = Pred()) {
+                                              const Sel &sel = Sel()) {
     const SegDesc &d = info.desc;
     const uint32_t type = d.flags & FLAG_TYPE_MASK;
     const int64_t end = s.end_time[i];
@@ -89,10 +111,14 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
         const uint4 vt = s.timestamps.views[i];
         const uint8_t *ts_bytes = view_data(s.timestamps, i, vt);
         if (type != MDB_MACAQUE_V_ID && n_res == 0) {
+            uint64_t row = 0; // (a running count, not k - k_lo: the two differ for a malformed, unsorted stream)
             decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error,
                                         [&](uint32_t, int64_t t) {
-                                            if (t >= t_lo && t <= t_hi)
-                                                { const float v = model_value_at(d, type, t); if (pred.pass(v)) acc.point(v); }
+                                            if (t >= t_lo && t <= t_hi) {
+                                                const float v = model_value_at(d, type, t);
+                                                if (sel.counts(v, row)) acc.point(v);
+                                                row += 1;
+                                            }
                                         });
             return;
         }
@@ -107,14 +133,14 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
                                         }
                                     });
         if (k_lo == 0xffffffffu) return;
-        // Timestamps are sorted, so the in-range points are exactly the indices k_lo..k_hi.
+        // Timestamps are sorted, so the in-range points are exactly the indices k_lo..k_hi; point k is row k - k_lo.
         float seed = d.value;
         if (type == MDB_MACAQUE_V_ID) {
             const uint4 vv = s.values.views[i];
             uint32_t last_bits = 0;
             decode_macaque_v(view_data(s.values, i, vv), vv.x, d.n_model, false, 0, error,
                              [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
+                                 if (k >= k_lo && k <= k_hi) { if (sel.counts(__uint_as_float(bits), k - k_lo)) acc.point(__uint_as_float(bits)); }
                                  last_bits = bits;
                              });
             seed = __uint_as_float(last_bits);
@@ -122,7 +148,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, d.n_model, error,
                                         [&](uint32_t k, int64_t t) {
                                             if (k >= k_lo && k <= k_hi)
-                                                { const float v = model_value_at(d, type, t); if (pred.pass(v)) acc.point(v); }
+                                                { const float v = model_value_at(d, type, t); if (sel.counts(v, k - k_lo)) acc.point(v); }
                                         });
         }
         if (n_res > 0) {
@@ -130,36 +156,18 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
             decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, n_res, true,
                              __float_as_uint(seed), error, [&](uint32_t k, uint32_t bits) {
                                  uint32_t index = d.n_model + k;
-                                 if (index >= k_lo && index <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
+                                 if (index >= k_lo && index <= k_hi) { if (sel.counts(__uint_as_float(bits), index - k_lo)) acc.point(__uint_as_float(bits)); }
                              });
         }
         return;
     }
 
-    // Regular timestamps start + k * delta: the in-range indices are an interval [k_lo, k_hi].
+    // Regular timestamps start + k * delta: the in-range indices are an interval [k_lo, k_hi]; point k is row k - k_lo.
     uint32_t k_lo = 0, k_hi = 0;
     if (!regular_index_interval(d.start, d.delta, d.n_total, t_lo, t_hi, &k_lo, &k_hi)) return;
 
     // Model part [a, b] of the interval.
-    if (type != MDB_MACAQUE_V_ID && k_lo < d.n_model) {
-        const uint32_t a = k_lo;
-        const uint32_t b = min(k_hi, d.n_model - 1);
-        if constexpr (Pred::always) {
-            model_closed_form(d, type, a, b, acc);
-        } else {
-            // The passing points of the model part: none, one interval in closed form, or (an end is NaN) one by one.
-            uint32_t ra = a, rb = b;
-            const int run = model_run(d, type, a, b, pred, &ra, &rb);
-            if (run == RUN_INTERVAL) {
-                model_closed_form(d, type, ra, rb, acc);
-            } else if (run == RUN_POINTS) {
-                for (uint32_t k = a; k <= b; k++) {
-                    const float v = model_value_at(d, type, d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta));
-                    if (pred.pass(v)) acc.point(v);
-                }
-            }
-        }
-    }
+    if (type != MDB_MACAQUE_V_ID && k_lo < d.n_model) sel.model(d, type, k_lo, min(k_hi, d.n_model - 1), 0, acc);
     float seed = d.value;
     if (type == MDB_MACAQUE_V_ID) {
         const uint4 vv = s.values.views[i];
@@ -170,7 +178,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
         if (k_lo < d.n_model || residuals_in_range) {
             decode_macaque_v(view_data(s.values, i, vv), vv.x, upto, false, 0, error,
                              [&](uint32_t k, uint32_t bits) {
-                                 if (k >= k_lo && k <= k_hi) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
+                                 if (k >= k_lo && k <= k_hi) { if (sel.counts(__uint_as_float(bits), k - k_lo)) acc.point(__uint_as_float(bits)); }
                                  last_bits = bits;
                              });
         }
@@ -182,7 +190,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
         decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, upto, true, __float_as_uint(seed),
                          error, [&](uint32_t k, uint32_t bits) {
                              uint32_t index = d.n_model + k;
-                             if (index >= k_lo) { if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits)); }
+                             if (index >= k_lo) { if (sel.counts(__uint_as_float(bits), index - k_lo)) acc.point(__uint_as_float(bits)); }
                          });
     }
 }

@@ -68,21 +68,18 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_span(DevSegments 
     counts[i] = count;
 }
 
-struct BucketCountOf {
-    const unsigned long long *counts;
-    __device__ uint64_t operator()(uint64_t i) const { return counts[i]; }
-};
-
 // The pairs of a segment whose points are a bit stream (MacaqueV values, irregular timestamps): slots [j0, j1) of the
 // slice, buckets b_first + (j - off). Pass 1 leaves each slot's index interval [k_lo, k_hi] of points in its sum
 // field (k_lo > k_hi: no point); pass 2 decodes the values once, each into the slot whose interval holds it, and
 // overwrites every slot with its partial. Returns false when the timestamps turn out not to be sorted (a malformed
-// stream): the caller then overwrites the slots with segment_range pair by pair, which tests every point. `pred` is
-// tested where a point is accumulated, nowhere else: the slots, the decode and the tail's seed are the unfiltered ones.
+// stream): the caller then overwrites the slots with segment_range pair by pair, which tests every point. `pred` (a
+// selector by value: rows are not counted here) is tested where a point is accumulated, nowhere else: the slots, the
+// decode and the tail's seed are the unfiltered ones.
 template <typename Pred>
 __device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const SegInfo &info, const BucketRequest &r,
                                        uint64_t off, uint64_t b_first, uint64_t j0, uint64_t j1, uint64_t p0,
                                        BucketPartial *__restrict__ out, uint32_t *error, const Pred &pred) {
+    static_assert(!Pred::by_row, "the buckets select by value: rows are not threaded through them");
     const SegDesc &d = info.desc;
     const uint32_t type = d.flags & FLAG_TYPE_MASK;
     const int64_t end = s.end_time[i];
@@ -140,7 +137,7 @@ __device__ bool bucket_stream_partials(const DevSegments &s, uint64_t i, const S
     };
     auto visit = [&](uint32_t k, float v) {
         while (j < j1 && k > current.y) flush();
-        if (j < j1 && k >= current.x && pred.pass(v)) acc.point(v);
+        if (j < j1 && k >= current.x && pred.counts(v, 0)) acc.point(v);
     };
     if (needed > 0) {
         float seed = d.value;
@@ -184,6 +181,7 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegme
                                                                         unsigned int *__restrict__ error_out,
                                                                         const unsigned long long *__restrict__ piece_base,
                                                                         Pred pred) {
+    static_assert(!Pred::by_row, "the buckets select by value: rows are not threaded through them");
     const uint64_t i = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
     if (i >= s.n) return;
     const uint64_t off = offsets[i], stop = offsets[i + 1];
@@ -285,8 +283,6 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_fold(BucketTree t
     cells[key] = cell;
 }
 
-static uint64_t align_256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
-
 static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + BUCKET_THREADS - 1) / BUCKET_THREADS); }
 
 static uint64_t slice_pairs_setting() {
@@ -325,19 +321,20 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
 
     // Span: pair offsets and the read-back words (total pairs, error, unsorted).
     void *p;
-    const uint64_t offsets_bytes = align_256((n + 1) * 8), sums_bytes = align_256(scan_block_sums_bytes(n));
+    const uint64_t offsets_bytes = align_up((n + 1) * 8, 256), sums_bytes = align_up(scan_block_sums_bytes(n), 256);
     if (scratch_reserve(ctx, SCRATCH_BUCKET_SPAN, 2 * offsets_bytes + sums_bytes + 256, &p)) return 1;
-    unsigned long long *counts = static_cast<unsigned long long *>(p);
-    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + offsets_bytes);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + 2 * offsets_bytes);
-    unsigned int *words = reinterpret_cast<unsigned int *>(static_cast<char *>(p) + 2 * offsets_bytes + sums_bytes);
+    Carver span(p);
+    unsigned long long *counts = span.take<unsigned long long>(n + 1);
+    unsigned long long *offsets = span.take<unsigned long long>(n + 1);
+    unsigned long long *block_sums = span.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
+    unsigned int *words = span.take<unsigned int>(2);
     MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
     {
         LaunchTimer timer(ctx, "k_agg_bucket_span");
         hipLaunchKernelGGL(k_agg_bucket_span, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, r,
                            counts, words);
     }
-    if (device_exclusive_scan(ctx, BucketCountOf{counts}, n, offsets, block_sums, "k_agg_bucket_scan")) return 1;
+    if (device_exclusive_scan(ctx, ItemsOf<unsigned long long>{counts}, n, offsets, block_sums, "k_agg_bucket_scan")) return 1;
     unsigned long long total = 0;
     unsigned int span_error = 0;
     MDB_HIP_CHECK(hipMemcpyAsync(&total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -371,10 +368,11 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
             MDB_HIP_CHECK(hipMemcpyAsync(cells, dev_cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToDevice,
                                          ctx->stream));
     }
-    const uint64_t partials_bytes = align_256(cap * sizeof(BucketPartial));
+    const uint64_t partials_bytes = align_up(cap * sizeof(BucketPartial), 256);
     if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, partials_bytes + cap * 8, &p)) return 1;
-    BucketPartial *partials = static_cast<BucketPartial *>(p);
-    unsigned long long *keys = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + partials_bytes);
+    Carver pairs_scratch(p);
+    BucketPartial *partials = pairs_scratch.take<BucketPartial>(cap);
+    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
     // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries.
     uint64_t tree_entries = 0;
     for (uint64_t m = cap; m > BUCKET_TILE;) {
@@ -423,16 +421,17 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
         tree.n[0] = m;
         tree.order = nullptr;
         if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            const uint64_t keys_bytes = align_256(m * 8), order_bytes = align_256(m * 4);
+            const uint64_t keys_bytes = align_up(m * 8, 256), order_bytes = align_up(m * 4, 256);
             size_t sort_bytes = 0;
             MDB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys, static_cast<uint32_t *>(nullptr),
                                                     static_cast<uint32_t *>(nullptr), (size_t)m, 0u, key_bits,
                                                     ctx->stream));
             if (scratch_reserve(ctx, SCRATCH_BUCKET_SORT, keys_bytes + 2 * order_bytes + sort_bytes, &p)) return 1;
-            unsigned long long *sorted_keys = static_cast<unsigned long long *>(p);
-            uint32_t *order_in = reinterpret_cast<uint32_t *>(static_cast<char *>(p) + keys_bytes);
-            uint32_t *order = reinterpret_cast<uint32_t *>(static_cast<char *>(p) + keys_bytes + order_bytes);
-            void *sort_storage = static_cast<char *>(p) + keys_bytes + 2 * order_bytes;
+            Carver sort_scratch(p);
+            unsigned long long *sorted_keys = sort_scratch.take<unsigned long long>(m);
+            uint32_t *order_in = sort_scratch.take<uint32_t>(m);
+            uint32_t *order = sort_scratch.take<uint32_t>(m);
+            void *sort_storage = sort_scratch.at;
             LaunchTimer timer(ctx, "k_agg_bucket_sort");
             hipLaunchKernelGGL(k_agg_bucket_iota, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, order_in, m);
             MDB_HIP_CHECK(rocprim::radix_sort_pairs(sort_storage, sort_bytes, keys, sorted_keys, order_in, order,
@@ -481,9 +480,7 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
 // but still has its group ids checked: buckets_run runs as for any range).
 static int bucket_filter_check(const mdb_bucket_request *request, const mdb_value_filter *filter, uint64_t *n_cells,
                                ValueKeys *keys, mdb_bucket_request *narrowed) {
-    if (bucket_request_check(request, n_cells)) return 1;
-    if (!value_keys_fold(*filter, keys))
-        return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
+    if (bucket_request_check(request, n_cells) || value_keys_fold(filter, keys)) return 1;
     *narrowed = *request;
     narrowed->t_lo = std::max(request->t_lo, filter->t_lo);
     narrowed->t_hi = std::min(request->t_hi, filter->t_hi);

@@ -15,13 +15,17 @@
 //                        residual tail is per point on its own; its segment's model part is classified as above.
 //   per-point segments   gathered into a batch of their own (k_filter_gather: the columns, with the same payload
 //                        buffers) and rebuilt by the range grid itself (grid_batch_dev_locked) in slices of at most
-//                        MDB_FILTER_SLICE_POINTS points (less under mdb_set_scratch_limit); k_filter_points then
-//                        compacts each segment's rows with one wave: __ballot of the predicate, a prefix from
-//                        __popcll, stable. Such segments are rebuilt twice (once to count, once to write) unless all
-//                        of them fit into one slice, which is then kept between the passes.
+//                        MDB_FILTER_SLICE_POINTS points (less under mdb_set_scratch_limit; filter_tested_slices);
+//                        k_filter_points_count / k_filter_points_write then compact each segment's rows with one wave
+//                        (slice_walk, mdb_filter_points.hpp: the walk the row masks' k_mask_points_* share): __ballot
+//                        of the predicate, a prefix from __popcll, stable. Such segments are rebuilt twice (once to
+//                        count, once to write) unless all of them fit into one slice, which is then kept between the
+//                        passes.
 //   scan                 rows per segment -> 64-bit output offsets (mdb_scan.hpp); one read-back sizes the output.
 //   k_filter_write_runs  1 wave / interval segment: start + k * delta and its model value for k in [a, b].
 // Rows come out in segment order and point order, exactly mdb_grid_batch_range's rows minus the ones that fail.
+// Also here, for the row masks (mdb_mask.hip) and the plain grid (mdb_grid.hip) too: what a count leaves for its write
+// (filter_count_done) and the result block of the owned forms (result_layout, owned_block_copy, owned_result_make).
 // All writes are ordinary vector stores; the only atomics are integer ones on LDS and on the three row counters.
 //
 // The filtered aggregates are k_agg_range's loop with the predicate (mdb_agg.hip, k_agg_filter): segment_range's
@@ -44,7 +48,7 @@ constexpr uint64_t FILTER_SLICE_DEFAULT = 1ull << 24; // points per slice of the
 
 // (FilterRun, classify_segment, Gathered, FilterPass: mdb_filter_points.hpp - shared with the row masks)
 
-// counts[i]: the passing model points of segment i's interval (its final row count once k_filter_points has added
+// counts[i]: the passing model points of segment i's interval (its final row count once k_filter_points_count has added
 // the per-point ones). per_point[i]: 0 - no point of segment i is tested one by one; 1 + m - its rows in the range
 // grid are tested from the (m + 1)-th on (m: the model rows the interval has already decided).
 __global__ __launch_bounds__(FILTER_THREADS) void k_filter_classify(DevSegments s, int64_t t_lo, int64_t t_hi,
@@ -65,10 +69,6 @@ struct FilterTested { // (scan functor: the segments with points tested one by o
     const uint32_t *per_point;
     __device__ uint64_t operator()(uint64_t i) const { return per_point[i] != 0 ? 1u : 0u; }
 };
-struct FilterRows { // (scan functor: rows per segment)
-    const uint32_t *rows;
-    __device__ uint64_t operator()(uint64_t i) const { return rows[i]; }
-};
 
 __global__ __launch_bounds__(FILTER_THREADS) void k_filter_gather(DevSegments s, const uint32_t *__restrict__ per_point,
                                                                   const unsigned long long *__restrict__ position,
@@ -88,39 +88,31 @@ __global__ __launch_bounds__(FILTER_THREADS) void k_filter_gather(DevSegments s,
     g.skip[j] = per_point[i] - 1;
 }
 
-// One wave per per-point segment of a slice (rows [first[j], first[j + 1]) of the slice's range grid, gathered
-// segment j0 + j): the passing rows behind the first skip ones. WRITE = false adds their number to counts[origin];
-// WRITE = true writes them, in order, behind the segment's interval rows.
-template <bool WRITE>
-__global__ __launch_bounds__(FILTER_THREADS) void k_filter_points(
+// The per-point segments of a slice (slice_walk, mdb_filter_points.hpp), their rows tested by value: the passing ones
+// added to counts[origin] ...
+__global__ __launch_bounds__(FILTER_THREADS) void k_filter_points_count(const float *__restrict__ slice_val,
+                                                                        const unsigned long long *__restrict__ first,
+                                                                        uint64_t n_slice, uint64_t j0, Gathered g,
+                                                                        ValueKeys keys, uint32_t *__restrict__ counts) {
+    slice_walk(first, n_slice, j0, g, [&](uint32_t, uint64_t) { return [&](uint64_t row) { return keys.pass(slice_val[row]); }; },
+               [](uint32_t, uint64_t) { return [](uint64_t, uint64_t, bool, unsigned long long, uint64_t) {}; },
+               [&](uint32_t origin, uint64_t kept) {
+                   if ((threadIdx.x & (MDB_WAVE - 1)) == 0) counts[origin] += (uint32_t)kept;
+               });
+}
+// ... or written, in order, behind the segment's interval rows.
+__global__ __launch_bounds__(FILTER_THREADS) void k_filter_points_write(
     const int64_t *__restrict__ slice_ts, const float *__restrict__ slice_val, const unsigned long long *__restrict__ first,
-    uint64_t n_slice, uint64_t j0, Gathered g, ValueKeys keys, uint32_t *__restrict__ counts,
-    const FilterRun *__restrict__ runs, const unsigned long long *__restrict__ offsets, int64_t *__restrict__ out_ts,
-    float *__restrict__ out_val) {
-    const uint32_t lane = threadIdx.x & (MDB_WAVE - 1);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const uint64_t waves = (uint64_t)gridDim.x * (FILTER_THREADS / MDB_WAVE);
-    for (uint64_t j = (uint64_t)blockIdx.x * (FILTER_THREADS / MDB_WAVE) + threadIdx.x / MDB_WAVE; j < n_slice; j += waves) {
-        const uint32_t origin = g.origin[j0 + j];
-        const uint64_t end = first[j + 1];
-        uint64_t out = 0;
-        if (WRITE) out = offsets[origin] + runs[origin].n;
-        uint64_t kept = 0;
-        for (uint64_t row0 = first[j] + g.skip[j0 + j]; row0 < end; row0 += MDB_WAVE) {
-            const uint64_t row = row0 + lane;
-            const bool in = row < end;
-            const float v = in ? slice_val[row] : 0.0f;
-            const bool pass = in && keys.pass(v);
-            const unsigned long long mask = __ballot(pass);
-            if (WRITE && pass) {
-                const uint64_t at = out + kept + (uint64_t)__popcll(mask & below);
-                out_ts[at] = slice_ts[row];
-                out_val[at] = v;
-            }
-            kept += (uint64_t)__popcll(mask);
-        }
-        if (!WRITE && lane == 0) counts[origin] += (uint32_t)kept;
-    }
+    uint64_t n_slice, uint64_t j0, Gathered g, ValueKeys keys, const FilterRun *__restrict__ runs,
+    const unsigned long long *__restrict__ offsets, int64_t *__restrict__ out_ts, float *__restrict__ out_val) {
+    slice_walk(first, n_slice, j0, g, [&](uint32_t, uint64_t) { return [&](uint64_t row) { return keys.pass(slice_val[row]); }; },
+               [&](uint32_t origin, uint64_t) {
+                   const uint64_t out = offsets[origin] + runs[origin].n;
+                   return [&, out](uint64_t, uint64_t row, bool pass, unsigned long long ballot, uint64_t kept) {
+                       slice_write_row(out + kept, row, pass, ballot, slice_ts, slice_val, out_ts, out_val);
+                   };
+               },
+               [](uint32_t, uint64_t) {});
 }
 
 // One wave per interval segment: its n points from offsets[i] on.
@@ -135,9 +127,11 @@ __global__ __launch_bounds__(FILTER_THREADS) void k_filter_write_runs(const Filt
         if (r.n == 0) continue;
         const uint64_t base = offsets[i];
         for (uint32_t k = lane; k < r.n; k += MDB_WAVE) {
-            const int64_t t = r.start + (int64_t)((uint64_t)k * (uint64_t)r.delta);
+            int64_t t;
+            float v;
+            run_point(r, k, &t, &v);
             out_ts[base + k] = t;
-            out_val[base + k] = r.type == MDB_SWING_ID ? (float)(r.slope * (double)t + r.intercept) : r.value;
+            out_val[base + k] = v;
         }
     }
 }
@@ -174,12 +168,6 @@ uint64_t slice_points(const mdb_ctx *ctx) {
     return points;
 }
 
-int fold_filter(const mdb_value_filter *filter, ValueKeys *keys) {
-    if (!value_keys_fold(*filter, keys))
-        return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
-    return 0;
-}
-
 } // namespace
 
 // The range grid of gathered segments [j0, j1) into the slice buffers, and the first row of each.
@@ -198,7 +186,7 @@ int filter_rebuild_slice(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1) 
     if (grid_batch_dev_locked(ctx, &part, TimeRange{f.t_lo, f.t_hi, 1}, f.slice_ts, f.slice_val, f.slice_rows,
                               f.slice_cap, &produced, nullptr))
         return 1;
-    return device_exclusive_scan(ctx, FilterRows{f.slice_rows}, part.n, f.slice_first, f.slice_block_sums,
+    return device_exclusive_scan(ctx, ItemsOf<uint32_t>{f.slice_rows}, part.n, f.slice_first, f.slice_block_sums,
                                  "k_filter_scan");
 }
 
@@ -218,23 +206,18 @@ int filter_gather_tested(mdb_ctx *ctx, FilterPass &f, const uint32_t *per_point,
         const uint64_t m = f.n_tested;
         const uint64_t b8 = align_up(m * 8, 256), b4 = align_up(m * 4, 256), b16 = align_up(m * 16, 256), b1 = align_up(m, 256);
         if (scratch_reserve(ctx, SCRATCH_FILTER_GATHER, b1 + 2 * b8 + 5 * b4 + 3 * b16, &p)) return 1;
-        uint8_t *at = static_cast<uint8_t *>(p);
-        auto take = [&at](uint64_t bytes) {
-            uint8_t *here = at;
-            at += bytes;
-            return here;
-        };
-        f.g.start = reinterpret_cast<int64_t *>(take(b8));
-        f.g.end = reinterpret_cast<int64_t *>(take(b8));
-        f.g.ts_views = reinterpret_cast<uint4 *>(take(b16));
-        f.g.value_views = reinterpret_cast<uint4 *>(take(b16));
-        f.g.residual_views = reinterpret_cast<uint4 *>(take(b16));
-        f.g.min = reinterpret_cast<float *>(take(b4));
-        f.g.max = reinterpret_cast<float *>(take(b4));
-        f.g.origin = reinterpret_cast<uint32_t *>(take(b4));
-        f.g.skip = reinterpret_cast<uint32_t *>(take(b4));
-        f.g.rows = reinterpret_cast<uint32_t *>(take(b4));
-        f.g.type = reinterpret_cast<int8_t *>(take(b1));
+        Carver gathered(p);
+        f.g.start = gathered.take<int64_t>(m);
+        f.g.end = gathered.take<int64_t>(m);
+        f.g.ts_views = gathered.take<uint4>(m);
+        f.g.value_views = gathered.take<uint4>(m);
+        f.g.residual_views = gathered.take<uint4>(m);
+        f.g.min = gathered.take<float>(m);
+        f.g.max = gathered.take<float>(m);
+        f.g.origin = gathered.take<uint32_t>(m);
+        f.g.skip = gathered.take<uint32_t>(m);
+        f.g.rows = gathered.take<uint32_t>(m);
+        f.g.type = gathered.take<int8_t>(m);
         {
             LaunchTimer timer(ctx, "k_filter_gather");
             hipLaunchKernelGGL(k_filter_gather, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, s, per_point, position,
@@ -279,18 +262,19 @@ int filter_gather_tested(mdb_ctx *ctx, FilterPass &f, const uint32_t *per_point,
         const uint64_t srows = align_up(m * 4, 256), sfirst = align_up((m + 1) * 8, 256);
         if (scratch_reserve(ctx, SCRATCH_FILTER_SLICE, sts + sval + srows + sfirst + align_up(scan_block_sums_bytes(m), 256), &p))
             return 1;
-        uint8_t *slice = static_cast<uint8_t *>(p);
-        f.slice_ts = reinterpret_cast<int64_t *>(slice);
-        f.slice_val = reinterpret_cast<float *>(slice + sts);
-        f.slice_rows = reinterpret_cast<uint32_t *>(slice + sts + sval);
-        f.slice_first = reinterpret_cast<unsigned long long *>(slice + sts + sval + srows);
-        f.slice_block_sums = reinterpret_cast<unsigned long long *>(slice + sts + sval + srows + sfirst);
+        Carver slice(p);
+        f.slice_ts = slice.take<int64_t>(cap);
+        f.slice_val = slice.take<float>(cap);
+        f.slice_rows = slice.take<uint32_t>(m);
+        f.slice_first = slice.take<unsigned long long>(m + 1);
+        f.slice_block_sums = slice.take<unsigned long long>(scan_block_sums_bytes(m) / 8);
     }
     return 0;
 }
 
-int filter_rows_by_type(mdb_ctx *ctx, const int8_t *types, const uint32_t *counts, uint64_t n,
-                        unsigned long long *by_type) {
+// by_type[k] (three words in HBM) = the sum of counts[i] over the segments of model type k.
+static int filter_rows_by_type(mdb_ctx *ctx, const int8_t *types, const uint32_t *counts, uint64_t n,
+                               unsigned long long *by_type) {
     MDB_HIP_CHECK(hipMemsetAsync(by_type, 0, 3 * 8, ctx->stream));
     if (n == 0) return 0;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS - 1) / FILTER_THREADS, 1024);
@@ -299,27 +283,79 @@ int filter_rows_by_type(mdb_ctx *ctx, const int8_t *types, const uint32_t *count
     return 0;
 }
 
-namespace {
-
-void launch_points(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1, bool write, int64_t *out_ts, float *out_val) {
-    const uint64_t n = j1 - j0;
-    if (n == 0) return;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS / MDB_WAVE - 1) / (FILTER_THREADS / MDB_WAVE), 8192);
-    LaunchTimer timer(ctx, write ? "k_filter_points_write" : "k_filter_points_count");
-    if (write)
-        hipLaunchKernelGGL(k_filter_points<true>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
-                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
-    else
-        hipLaunchKernelGGL(k_filter_points<false>, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.slice_ts,
-                           f.slice_val, f.slice_first, n, j0, f.g, f.keys, f.counts, f.runs, f.offsets, out_ts, out_val);
+int filter_count_done(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *counts, unsigned long long *offsets,
+                      unsigned long long *block_sums, unsigned long long *by_type, const char *scan_name, uint64_t *total,
+                      mdb_grid_metrics *metrics) {
+    const uint64_t n = in->n;
+    if (device_exclusive_scan(ctx, ItemsOf<uint32_t>{counts}, n, offsets, block_sums, scan_name)) return 1;
+    if (filter_rows_by_type(ctx, in->model_type_id, counts, n, by_type)) return 1;
+    unsigned long long words[4] = {0, 0, 0, 0};
+    MDB_HIP_CHECK(hipMemcpyAsync(&words[0], offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipMemcpyAsync(&words[1], by_type, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    *total = words[0];
+    metrics->rows_created = words[0];
+    for (int k = 0; k < 3; k++) metrics->rows_created_by_model_type[k] = words[1 + k];
+    return 0;
 }
+
+ResultLayout result_layout(uint64_t reserve_front, uint64_t n, uint64_t n_segments, bool values_only) {
+    const uint64_t front = align_up(reserve_front, 4); // keeps the 16-byte store alignment
+    return ResultLayout{front, n, n_segments, values_only ? 0 : align_up((front + n) * 8, 256), align_up((front + n) * 4, 256),
+                        align_up(n_segments * 4, 256), values_only};
+}
+
+int owned_block_copy(mdb_ctx *ctx, const void *stage, const ResultLayout &layout, void **block, uint64_t *capacity) {
+    if (ctx->pinned_pool->take(layout.bytes(), block, capacity)) return 1;
+    if (!stage) {
+        std::memset(layout.rows(*block), 0, layout.rows_bytes);
+    } else if (hipMemcpyAsync(*block, stage, layout.bytes(), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
+        ctx->pinned_pool->give(*block, *capacity);
+        return fail("hipMemcpy device to host failed.");
+    }
+    return 0;
+}
+
+int owned_result_make(mdb_ctx *ctx, int rc, const ResultLayout &layout, void *block, uint64_t capacity,
+                      const mdb_grid_metrics &metrics, mdb_grid_result **out) {
+    if (rc) {
+        ctx->pinned_pool->give(block, capacity);
+        return rc;
+    }
+    OwnedGridResult *result = new OwnedGridResult();
+    result->c.timestamps = layout.timestamps(block);
+    result->c.values = layout.values(block);
+    result->c.rows_per_segment = layout.rows(block);
+    result->c.n = layout.n;
+    result->c.n_segments = layout.n_segments;
+    result->c.reserved_front = layout.front;
+    result->c.metrics = metrics;
+    result->c.priv_ = result;
+    result->pool = ctx->pinned_pool;
+    result->block = block;
+    result->capacity = capacity;
+    *out = &result->c;
+    return 0;
+}
+
+int owned_result(mdb_ctx *ctx, const void *stage, const ResultLayout &layout, const mdb_grid_metrics &metrics,
+                 mdb_grid_result **out) {
+    void *block = nullptr;
+    uint64_t capacity = 0;
+    if (owned_block_copy(ctx, stage, layout, &block, &capacity)) return 1;
+    const int rc = stage && hipStreamSynchronize(ctx->stream) != hipSuccess ? fail("hipMemcpy device to host failed.") : 0;
+    return owned_result_make(ctx, rc, layout, block, capacity, metrics, out);
+}
+
+namespace {
 
 // Pass 1: classify, count the per-point segments' passing rows (slice by slice), scan. Sets f.total and f.metrics.
 int filter_count(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, FilterPass &f) {
     f.in = in;
     f.t_lo = filter->t_lo;
     f.t_hi = filter->t_hi;
-    if (fold_filter(filter, &f.keys)) return 1;
+    if (value_keys_fold(filter, &f.keys)) return 1;
     // The range grid's prepass: its segment counters and its verdict on the segments.
     uint64_t range_total = 0;
     if (grid_range_plan(ctx, in, f.t_lo, f.t_hi, &range_total, &f.metrics, nullptr)) return 1;
@@ -332,39 +368,27 @@ int filter_count(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *f
     void *p = nullptr;
     if (scratch_reserve(ctx, SCRATCH_FILTER_SEGMENTS, runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes + 256, &p))
         return 1;
-    uint8_t *base = static_cast<uint8_t *>(p);
-    f.runs = reinterpret_cast<FilterRun *>(base);
-    f.counts = reinterpret_cast<uint32_t *>(base + runs_bytes);
-    uint32_t *per_point = reinterpret_cast<uint32_t *>(base + runs_bytes + words_bytes);
-    f.offsets = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes);
-    unsigned long long *position = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + offsets_bytes);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes);
-    unsigned long long *by_type = reinterpret_cast<unsigned long long *>(base + runs_bytes + 2 * words_bytes + 2 * offsets_bytes + sums_bytes);
+    Carver segments(p);
+    f.runs = segments.take<FilterRun>(n);
+    f.counts = segments.take<uint32_t>(n);
+    uint32_t *per_point = segments.take<uint32_t>(n);
+    f.offsets = segments.take<unsigned long long>(n + 1);
+    unsigned long long *position = segments.take<unsigned long long>(n + 1);
+    unsigned long long *block_sums = segments.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
+    unsigned long long *by_type = segments.take<unsigned long long>(3);
     const uint32_t blocks = (uint32_t)((n + FILTER_THREADS - 1) / FILTER_THREADS);
     {
         LaunchTimer timer(ctx, "k_filter_classify");
         hipLaunchKernelGGL(k_filter_classify, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, s, f.t_lo, f.t_hi,
                            f.keys, f.runs, f.counts, per_point);
     }
-    if (filter_gather_tested(ctx, f, per_point, position, block_sums)) return 1;
-    if (f.n_tested > 0) {
-        for (const auto &range : f.slices) {
-            if (filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
-            launch_points(ctx, f, range.first, range.second, false, nullptr, nullptr);
-        }
-        f.kept = f.slices.size() == 1;
-    }
-    if (device_exclusive_scan(ctx, FilterRows{f.counts}, n, f.offsets, block_sums, "k_filter_scan")) return 1;
-    if (filter_rows_by_type(ctx, in->model_type_id, f.counts, n, by_type)) return 1;
-    unsigned long long words[4] = {0, 0, 0, 0};
-    MDB_HIP_CHECK(hipMemcpyAsync(&words[0], f.offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipMemcpyAsync(&words[1], by_type, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    f.total = words[0];
-    f.metrics.rows_created = f.total;
-    for (int k = 0; k < 3; k++) f.metrics.rows_created_by_model_type[k] = words[1 + k];
-    return 0;
+    if (filter_tested_slices(ctx, f, per_point, position, block_sums, [&](uint64_t j0, uint64_t n_slice) {
+            LaunchTimer timer(ctx, "k_filter_points_count");
+            hipLaunchKernelGGL(k_filter_points_count, dim3(slice_walk_blocks(n_slice, 8192)), dim3(FILTER_THREADS), 0,
+                               ctx->stream, f.slice_val, f.slice_first, n_slice, j0, f.g, f.keys, f.counts);
+        }))
+        return 1;
+    return filter_count_done(ctx, in, f.counts, f.offsets, block_sums, by_type, "k_filter_scan", &f.total, &f.metrics);
 }
 
 // Pass 2: the rows into out_ts / out_val (f.total of them), rows per segment into out_rows (may be nullptr).
@@ -372,16 +396,18 @@ int filter_write(mdb_ctx *ctx, FilterPass &f, int64_t *out_ts, float *out_val, u
     const uint64_t n = f.in->n;
     if (n == 0) return 0;
     if (f.total > 0) {
-        const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + FILTER_THREADS / MDB_WAVE - 1) / (FILTER_THREADS / MDB_WAVE), 16384);
         {
             LaunchTimer timer(ctx, "k_filter_write_runs");
-            hipLaunchKernelGGL(k_filter_write_runs, dim3(blocks), dim3(FILTER_THREADS), 0, ctx->stream, f.runs, n,
-                               f.offsets, out_ts, out_val);
+            hipLaunchKernelGGL(k_filter_write_runs, dim3(slice_walk_blocks(n, 16384)), dim3(FILTER_THREADS), 0, ctx->stream,
+                               f.runs, n, f.offsets, out_ts, out_val);
         }
-        for (const auto &range : f.slices) {
-            if (!f.kept && filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
-            launch_points(ctx, f, range.first, range.second, true, out_ts, out_val);
-        }
+        if (filter_tested_slices(ctx, f, nullptr, nullptr, nullptr, [&](uint64_t j0, uint64_t n_slice) {
+                LaunchTimer timer(ctx, "k_filter_points_write");
+                hipLaunchKernelGGL(k_filter_points_write, dim3(slice_walk_blocks(n_slice, 8192)), dim3(FILTER_THREADS), 0,
+                                   ctx->stream, f.slice_ts, f.slice_val, f.slice_first, n_slice, j0, f.g, f.keys, f.runs,
+                                   f.offsets, out_ts, out_val);
+            }))
+            return 1;
     }
     if (out_rows) MDB_HIP_CHECK(hipMemcpyAsync(out_rows, f.counts, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
@@ -439,64 +465,27 @@ int mdb_grid_batch_filter_owned(mdb_ctx *ctx, const mdb_segments *in, const mdb_
                                 uint64_t reserve_front, mdb_grid_result **out) {
     if (!ctx || !in || !filter || !out) return fail("ctx, in, filter and out must not be NULL.");
     ValueKeys keys;
-    if (fold_filter(filter, &keys)) return 1;
+    if (value_keys_fold(filter, &keys)) return 1;
     mdb::CallGuard lock(ctx);
     MDB_HIP_CHECK(hipSetDevice(ctx->device));
     mdb_segments_owned *dev = nullptr;
     if (upload_segments_locked(ctx, in, true, &dev)) return 1;
-    const uint64_t n_segments = dev->seg.n;
-    OwnedGridResult *result = nullptr;
-    int rc = 0;
-    {
-        FilterPass f;
-        rc = filter_count(ctx, &dev->seg, filter, f);
-        // The device staging area mirrors the host block (same gaps), so one copy moves it all.
-        const uint64_t front = align_up(reserve_front, 4);
-        const uint64_t ts_bytes = align_up((front + f.total) * 8, 256), val_bytes = align_up((front + f.total) * 4, 256);
-        const uint64_t rows_bytes = align_up(n_segments * 4, 256);
-        void *stage = nullptr;
-        if (!rc) rc = scratch_reserve(ctx, SCRATCH_STAGE_DEV, ts_bytes + val_bytes + rows_bytes, &stage);
-        uint8_t *base = static_cast<uint8_t *>(stage);
-        if (!rc)
-            rc = filter_write(ctx, f, reinterpret_cast<int64_t *>(base) + front, reinterpret_cast<float *>(base + ts_bytes) + front,
-                              reinterpret_cast<uint32_t *>(base + ts_bytes + val_bytes));
-        void *block = nullptr;
-        uint64_t capacity = 0;
-        if (!rc) rc = ctx->pinned_pool->take(ts_bytes + val_bytes + rows_bytes, &block, &capacity);
-        if (!rc) {
-            if (hipMemcpyAsync(block, stage, ts_bytes + val_bytes + rows_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                hipStreamSynchronize(ctx->stream) != hipSuccess)
-                rc = fail("hipMemcpy device to host failed.");
-            if (rc) {
-                ctx->pinned_pool->give(block, capacity);
-            } else {
-                result = new OwnedGridResult();
-                uint8_t *host = static_cast<uint8_t *>(block);
-                result->c.timestamps = reinterpret_cast<int64_t *>(host) + front;
-                result->c.values = reinterpret_cast<float *>(host + ts_bytes) + front;
-                result->c.rows_per_segment = reinterpret_cast<uint32_t *>(host + ts_bytes + val_bytes);
-                result->c.n = f.total;
-                result->c.n_segments = n_segments;
-                result->c.reserved_front = front;
-                result->c.metrics = f.metrics;
-                result->c.priv_ = result;
-                result->pool = ctx->pinned_pool;
-                result->block = block;
-                result->capacity = capacity;
-            }
-        }
-    }
+    FilterPass f;
+    int rc = filter_count(ctx, &dev->seg, filter, f);
+    const ResultLayout layout = result_layout(reserve_front, f.total, dev->seg.n, false);
+    void *stage = nullptr;
+    if (!rc) rc = scratch_reserve(ctx, SCRATCH_STAGE_DEV, layout.bytes(), &stage);
+    if (!rc) rc = filter_write(ctx, f, layout.timestamps(stage), layout.values(stage), layout.rows(stage));
+    if (!rc) rc = owned_result(ctx, stage, layout, f.metrics, out);
     mdb_segments_free(dev);
-    if (rc) return 1;
-    *out = &result->c;
-    return 0;
+    return rc;
 }
 
 int mdb_agg_batch_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_filter *filter, uint32_t which_mask,
                              mdb_agg_state *inout) {
     if (!ctx || !in || !filter || !inout) return fail("ctx, in, filter and inout must not be NULL.");
     ValueKeys keys;
-    if (fold_filter(filter, &keys)) return 1;
+    if (value_keys_fold(filter, &keys)) return 1;
     mdb::CallGuard lock(ctx);
     MDB_HIP_CHECK(hipSetDevice(ctx->device));
     return agg_filter_run(ctx, in, filter->t_lo, filter->t_hi, keys, which_mask, inout);
@@ -514,7 +503,7 @@ int mdb_agg_batch_filter_list(mdb_ctx *ctx, const mdb_segments *const *inputs, u
     for (uint32_t k = 0; k < n_inputs; k++)
         if (!inputs[k]) return fail("A batch of the list is NULL.");
     ValueKeys keys;
-    if (fold_filter(filter, &keys)) return 1;
+    if (value_keys_fold(filter, &keys)) return 1;
     if (n_inputs == 0) return 0;
     mdb::CallGuard lock(ctx);
     MDB_HIP_CHECK(hipSetDevice(ctx->device));

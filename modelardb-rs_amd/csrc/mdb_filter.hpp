@@ -1,6 +1,6 @@
-// mdb_filter.hpp - the value predicate of mdb_value_filter (mdb_format.h) on the device, and the run of passing
-// points of a model: shared by the filtered aggregates (mdb_agg_dev.hpp's segment_range, mdb_agg.hip) and the
-// filtered grid (mdb_filter.hip).
+// mdb_filter.hpp - the value predicate of mdb_value_filter (mdb_format.h) on the device, the two selectors of
+// segment_range (mdb_agg_dev.hpp) that do not look at rows, and the run of passing points of a model: shared by the
+// filtered aggregates (mdb_agg.hip, mdb_buckets.hip), the filtered grid (mdb_filter.hip) and the row masks.
 #pragma once
 
 #include "mdb_segment_dev.hpp"
@@ -15,26 +15,42 @@ __host__ __device__ __forceinline__ int32_t total_order_key(uint32_t bits) {
     return (int32_t)(bits ^ ((uint32_t)((int32_t)bits >> 31) & 0x7fffffffu));
 }
 
-// The predicate of the existing calls: every value passes (the default of segment_range).
+struct RangeAcc; // (mdb_agg_dev.hpp)
+
+// A SELECTOR says which points of a segment the walk of mdb_agg_dev.hpp (segment_range) takes. It answers two
+// questions: counts(v, row) - does the point of value v, the row-th of the segment's points inside the time range,
+// count? - and model(d, type, a, b, row_a, acc): what the model points [a, b] of a PMC-Mean or Swing segment with
+// regular timestamps (point a is row row_a) add to acc. by_row: does it look at rows at all? Three of them: AllValues
+// and ValueKeys here, SegmentRows in mdb_mask.hpp. (model() of the two here: mdb_agg_dev.hpp, behind the closed form)
+
+// Every point counts (the range calls, the default of segment_range).
 struct AllValues {
-    static constexpr bool always = true;
-    __device__ __forceinline__ bool pass(float) const { return true; }
+    static constexpr bool by_row = false;
+    __device__ __forceinline__ bool counts(float, uint64_t) const { return true; }
+    __device__ __forceinline__ void model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t row_a,
+                                          RangeAcc &acc) const;
 };
 
 // The value bounds folded into one closed interval of keys [lo, hi] (lo > hi: nothing passes).
 struct ValueKeys {
-    static constexpr bool always = false;
+    static constexpr bool by_row = false;
     int32_t lo;
     int32_t hi;
     __device__ __forceinline__ bool key_passes(int32_t key) const { return key >= lo && key <= hi; }
     __device__ __forceinline__ bool pass(float v) const { return key_passes(total_order_key(__float_as_uint(v))); }
+    __device__ __forceinline__ bool counts(float v, uint64_t) const { return pass(v); }
+    __device__ __forceinline__ void model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t row_a,
+                                          RangeAcc &acc) const;
 };
 
 // Host: the flags folded into closed key bounds (an open end moves by one key; at the ±NaN ends there is no key
-// beyond, and the interval is empty). Returns false for unknown flag bits or reserved != 0.
-inline bool value_keys_fold(const mdb_value_filter &f, ValueKeys *out) {
+// beyond, and the interval is empty). What every entry point with a filter begins with: 0, or 1 and the message for
+// unknown flag bits or reserved != 0.
+inline int value_keys_fold(const mdb_value_filter *filter, ValueKeys *out) {
+    const mdb_value_filter &f = *filter;
     const uint32_t known = MDB_VALUE_LO_OPEN | MDB_VALUE_HI_OPEN | MDB_VALUE_NO_LO | MDB_VALUE_NO_HI;
-    if ((f.flags & ~known) != 0 || f.reserved != 0) return false;
+    if ((f.flags & ~known) != 0 || f.reserved != 0)
+        return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
     uint32_t lo_bits, hi_bits;
     std::memcpy(&lo_bits, &f.v_lo, 4);
     std::memcpy(&hi_bits, &f.v_hi, 4);
@@ -49,7 +65,7 @@ inline bool value_keys_fold(const mdb_value_filter &f, ValueKeys *out) {
         out->lo = (int32_t)lo;
         out->hi = (int32_t)hi;
     }
-    return true;
+    return 0;
 }
 
 // What a value predicate makes of the model points k in [a, b] of a PMC-Mean or Swing segment with regular

@@ -1,7 +1,8 @@
 // mdb_filter_points.hpp - what the filtered grid (mdb_filter.hip) and the row masks (mdb_mask.hip) share: the three
-// classes a time-clipped segment falls into under a value predicate (classify_segment), and the segments whose
-// points have to be looked at one by one, gathered into a batch of their own and rebuilt by the range grid in
-// bounded slices (FilterPass, filter_gather_tested, filter_rebuild_slice).
+// classes a time-clipped segment falls into under a value predicate (classify_segment), the k-th point of an interval
+// (run_point), and the segments whose points have to be looked at one by one, gathered into a batch of their own and
+// rebuilt by the range grid in bounded slices (FilterPass, filter_tested_slices) whose rows one wave per segment walks
+// 64 at a time (slice_walk); then what a count leaves for its write (filter_count_done).
 #pragma once
 
 #include "mdb_filter.hpp"
@@ -25,6 +26,13 @@ struct FilterRun {
     uint32_t pad;
 };
 static_assert(sizeof(FilterRun) == 48, "48 B per segment");
+
+// The k-th point of a run.
+__device__ __forceinline__ void run_point(const FilterRun &r, uint32_t k, int64_t *t, float *v) {
+    const int64_t time = r.start + (int64_t)((uint64_t)k * (uint64_t)r.delta);
+    *t = time;
+    *v = r.type == MDB_SWING_ID ? (float)(r.slope * (double)time + r.intercept) : r.value;
+}
 
 // Segment i under [t_lo, t_hi] and `keys`. *run: the passing model points of its interval (n == 0: none).
 // *tested: 0 - no point of the segment is tested one by one; 1 + m - its rows in the range grid are tested from the
@@ -88,6 +96,47 @@ struct Gathered {
     uint32_t *rows;      // rows of the range grid
 };
 
+// One wave per per-point segment of a slice (rows [first[j], first[j + 1]) of the slice's range grid, gathered
+// segment j0 + j, segment `origin` of the batch): its rows behind the first skip ones, 64 at a time. Per segment,
+// select_of(origin, begin) gives the test of a row and sink_of(origin, begin) what takes a round's outcome:
+// selected(row) of every lane's row -> __ballot -> take(row0, row, pass, ballot, kept), kept: the rows selected in the
+// rounds before. done(origin, kept) ends the segment.
+template <typename SelectOf, typename SinkOf, typename Done>
+__device__ __forceinline__ void slice_walk(const unsigned long long *__restrict__ first, uint64_t n_slice, uint64_t j0,
+                                           const Gathered &g, SelectOf select_of, SinkOf sink_of, Done done) {
+    const uint32_t lane = threadIdx.x & (MDB_WAVE - 1);
+    const uint64_t waves = (uint64_t)gridDim.x * (FILTER_THREADS / MDB_WAVE);
+    for (uint64_t j = (uint64_t)blockIdx.x * (FILTER_THREADS / MDB_WAVE) + threadIdx.x / MDB_WAVE; j < n_slice; j += waves) {
+        const uint32_t origin = g.origin[j0 + j];
+        const uint64_t begin = first[j], end = first[j + 1];
+        const auto selected = select_of(origin, begin);
+        const auto take = sink_of(origin, begin);
+        uint64_t kept = 0;
+        for (uint64_t row0 = begin + g.skip[j0 + j]; row0 < end; row0 += MDB_WAVE) {
+            const uint64_t row = row0 + lane;
+            const bool pass = row < end && selected(row);
+            const unsigned long long ballot = __ballot(pass);
+            take(row0, row, pass, ballot, kept);
+            kept += (uint64_t)__popcll(ballot);
+        }
+        done(origin, kept);
+    }
+}
+// (the sink of the two kernels that write: the selected rows, in order, from out[origin] on)
+__device__ __forceinline__ void slice_write_row(uint64_t out, uint64_t row, bool pass, unsigned long long ballot,
+                                                const int64_t *__restrict__ slice_ts, const float *__restrict__ slice_val,
+                                                int64_t *__restrict__ out_ts, float *__restrict__ out_val) {
+    if (!pass) return;
+    const uint32_t lane = threadIdx.x & (MDB_WAVE - 1);
+    const uint64_t at = out + (uint64_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    if (out_ts) out_ts[at] = slice_ts[row];
+    out_val[at] = slice_val[row];
+}
+inline uint32_t slice_walk_blocks(uint64_t n_slice, uint32_t most) { // (launches of one wave per segment)
+    const uint64_t per_block = FILTER_THREADS / MDB_WAVE;
+    return (uint32_t)((n_slice + per_block - 1) / per_block < most ? (n_slice + per_block - 1) / per_block : most);
+}
+
 // One filtered grid call over a batch in HBM: what the count leaves for the write.
 struct FilterPass {
     const mdb_segments *in = nullptr;
@@ -119,8 +168,24 @@ int filter_gather_tested(mdb_ctx *ctx, FilterPass &f, const uint32_t *per_point,
                          unsigned long long *block_sums);
 // The range grid of gathered segments [j0, j1) into the slice buffers, and the first row of each (f.slice_first).
 int filter_rebuild_slice(mdb_ctx *ctx, FilterPass &f, uint64_t j0, uint64_t j1);
-// by_type[k] (three words in HBM) = the sum of counts[i] over the segments of model type k.
-int filter_rows_by_type(mdb_ctx *ctx, const int8_t *types, const uint32_t *counts, uint64_t n,
-                        unsigned long long *by_type);
+// The per-point segments gathered (per_point nullptr: as an earlier pass over f left them), then every slice rebuilt
+// (unless it is the only one and still in place) and handed to launch(j0, n_slice).
+template <typename Launch>
+int filter_tested_slices(mdb_ctx *ctx, FilterPass &f, const uint32_t *per_point, unsigned long long *position,
+                         unsigned long long *block_sums, Launch launch) {
+    if (per_point && filter_gather_tested(ctx, f, per_point, position, block_sums)) return 1;
+    for (const auto &range : f.slices) {
+        if (!f.kept && filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
+        if (range.second > range.first) launch(range.first, range.second - range.first);
+    }
+    f.kept = f.slices.size() == 1;
+    return 0;
+}
+// What a count leaves for its write: counts[i] (the rows of segment i of `in`) scanned into offsets (n + 1), and read
+// back (one synchronisation) their total and, through by_type (three words in HBM), the rows of every model type:
+// rows_created and rows_created_by_model_type of *metrics.
+int filter_count_done(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *counts, unsigned long long *offsets,
+                      unsigned long long *block_sums, unsigned long long *by_type, const char *scan_name, uint64_t *total,
+                      mdb_grid_metrics *metrics);
 
 } // namespace mdb

@@ -4215,6 +4215,7 @@ __global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, B
                                                                 unsigned long long e0, unsigned long long e1,
                                                                 unsigned long long *__restrict__ keys,
                                                                 BucketPartial *__restrict__ out, Pred pred) {
+    static_assert(!Pred::by_row, "the buckets select by value: rows are not threaded through them");
     __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
     const int lane = threadIdx.x;
     const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
@@ -4272,7 +4273,7 @@ __global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, B
         const int64_t t = start + (int64_t)((uint64_t)(point_index + k) * (uint64_t)delta);
         const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
         while (bucket < b) flush();
-        if (pred.pass(__uint_as_float(bits))) acc.point(__uint_as_float(bits));
+        if (pred.counts(__uint_as_float(bits), 0)) acc.point(__uint_as_float(bits)); // (by value: Pred::by_row is false)
     };
     reader.begin();
     reader.top_up(ring, lane);
@@ -4901,58 +4902,30 @@ int mdb::grid_batch_owned_list(mdb_ctx *ctx, const mdb_segments *const *ins, uin
     if (upload_segment_list_locked(ctx, ins, n_ins, true, &dev)) return 1;
     const double t_uploaded = since_begin();
     double t_planned = t_uploaded, t_launched = t_uploaded, t_down = t_uploaded;
-    const uint64_t n_segments = dev->seg.n;
     int rc = 0;
-    OwnedGridResult *result = nullptr;
     {
         GridPlan plan;
         rc = grid_plan(ctx, &dev->seg, range, &plan);
         if (!rc) rc = mv_host_index_attach(ctx, dev->seg, index_piece_base, index_cursors, &plan.mv_index);
         t_planned = since_begin();
-        const uint64_t total = plan.host_header.total_points;
         // The device staging area mirrors the host block (same gaps), so one copy moves it all.
-        const uint64_t front = align_up(reserve_front, 4); // keeps the 16-byte store alignment
-        const uint64_t ts_bytes = values_only ? 0 : align_up((front + total) * 8, 256);
-        const uint64_t val_bytes = align_up((front + total) * 4, 256);
-        const uint64_t rows_bytes = align_up(n_segments * 4, 256);
+        const ResultLayout layout = result_layout(reserve_front, plan.host_header.total_points, dev->seg.n, values_only);
         void *stage = nullptr;
-        if (!rc) rc = scratch_reserve(ctx, SCRATCH_STAGE_DEV, ts_bytes + val_bytes + rows_bytes, &stage);
-        uint8_t *base = static_cast<uint8_t *>(stage);
-        if (!rc)
-            rc = grid_launch(ctx, &dev->seg, range, plan,
-                             values_only ? nullptr : reinterpret_cast<int64_t *>(base) + front,
-                             reinterpret_cast<float *>(base + ts_bytes) + front,
-                             reinterpret_cast<uint32_t *>(base + ts_bytes + val_bytes));
+        if (!rc) rc = scratch_reserve(ctx, SCRATCH_STAGE_DEV, layout.bytes(), &stage);
+        if (!rc) rc = grid_launch(ctx, &dev->seg, range, plan, layout.timestamps(stage), layout.values(stage), layout.rows(stage));
         t_launched = since_begin();
         void *block = nullptr;
         uint64_t capacity = 0;
-        if (!rc) rc = ctx->pinned_pool->take(ts_bytes + val_bytes + rows_bytes, &block, &capacity);
+        // One copy of the three columns (they are contiguous in the staging area) into the
+        // page-locked block; then the serial kernel's verdict.
         if (!rc) {
-            // One copy of the three columns (they are contiguous in the staging area) into the
-            // page-locked block; then the serial kernel's verdict.
-            if (hipMemcpyAsync(block, stage, ts_bytes + val_bytes + rows_bytes, hipMemcpyDeviceToHost,
-                               ctx->stream) != hipSuccess)
-                rc = fail("hipMemcpy device to host failed.");
+            const bool taken = (rc = owned_block_copy(ctx, stage, layout, &block, &capacity)) == 0;
             if (!rc) rc = grid_late_error(ctx, plan);
             t_down = since_begin();
-            if (rc) {
-                ctx->pinned_pool->give(block, capacity);
-            } else {
-                result = new OwnedGridResult();
-                uint8_t *host = static_cast<uint8_t *>(block);
-                result->c.timestamps = values_only ? nullptr : reinterpret_cast<int64_t *>(host) + front;
-                result->c.values = reinterpret_cast<float *>(host + ts_bytes) + front;
-                result->c.rows_per_segment = reinterpret_cast<uint32_t *>(host + ts_bytes + val_bytes);
-                result->c.n = total;
-                result->c.n_segments = n_segments;
-                result->c.reserved_front = front;
-                std::memset(&result->c.metrics, 0, sizeof(result->c.metrics));
-                fill_metrics(plan.host_header, &result->c.metrics);
-                result->c.priv_ = result;
-                result->pool = ctx->pinned_pool;
-                result->block = block;
-                result->capacity = capacity;
-            }
+            mdb_grid_metrics metrics;
+            std::memset(&metrics, 0, sizeof(metrics));
+            fill_metrics(plan.host_header, &metrics);
+            if (taken) rc = owned_result_make(ctx, rc, layout, block, capacity, metrics, out);
         }
     }
     mdb_segments_free(dev);
@@ -4971,9 +4944,7 @@ int mdb::grid_batch_owned_list(mdb_ctx *ctx, const mdb_segments *const *ins, uin
             entry.total_ms += phase.second;
         }
     }
-    if (rc) return 1;
-    *out = &result->c;
-    return 0;
+    return rc ? 1 : 0;
 }
 
 namespace {

@@ -46,6 +46,17 @@ GridPipeline *ctx_pipeline_detach(mdb_ctx *ctx);
 // the context's); they live until the context is closed.
 int pipeline_clones(mdb_ctx *ctx, mdb_ctx **out, int capacity);
 
+// Carves one reservation into arrays, each beginning on a 256-byte boundary of it: take<T>(count) is the next one.
+struct Carver {
+    uint8_t *at;
+    explicit Carver(void *base) : at(static_cast<uint8_t *>(base)) {}
+    template <typename T> T *take(uint64_t count) {
+        T *here = reinterpret_cast<T *>(at);
+        at += (count * sizeof(T) + 255) & ~255ull;
+        return here;
+    }
+};
+
 // Owner bookkeeping behind mdb_grid_result::priv_.
 struct OwnedGridResult {
     mdb_grid_result c;
@@ -56,6 +67,26 @@ struct OwnedGridResult {
     std::vector<std::pair<void *, uint64_t>> tag_blocks;
     std::vector<mdb_view16 *> tag_views; // per column: the view of the first reconstructed row
 };
+// A result block and the device staging area that mirrors it (the same gaps, so one copy moves it all): `front` rows
+// reserved in front of the n timestamps (none of either with values_only) and values, then n_segments rows_per_segment.
+struct ResultLayout {
+    uint64_t front, n, n_segments, ts_bytes, val_bytes, rows_bytes;
+    bool values_only;
+    uint64_t bytes() const { return ts_bytes + val_bytes + rows_bytes; }
+    int64_t *timestamps(void *base) const { return values_only ? nullptr : static_cast<int64_t *>(base) + front; }
+    float *values(void *base) const { return reinterpret_cast<float *>(static_cast<uint8_t *>(base) + ts_bytes) + front; }
+    uint32_t *rows(void *base) const { return reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(base) + ts_bytes + val_bytes); }
+};
+ResultLayout result_layout(uint64_t reserve_front, uint64_t n, uint64_t n_segments, bool values_only);
+// mdb_filter.hip: a page-locked block of the context's pool with the copy of the staging area `stage` into it
+// enqueued on the context's stream (stage nullptr: no copy, rows_per_segment zeroed); then, once the caller has
+// synchronised the stream and trusts the copy, the result that owns the block (rc != 0: the block goes back instead).
+// owned_result: both, with the synchronisation between them.
+int owned_block_copy(mdb_ctx *ctx, const void *stage, const ResultLayout &layout, void **block, uint64_t *capacity);
+int owned_result_make(mdb_ctx *ctx, int rc, const ResultLayout &layout, void *block, uint64_t capacity,
+                      const mdb_grid_metrics &metrics, mdb_grid_result **out);
+int owned_result(mdb_ctx *ctx, const void *stage, const ResultLayout &layout, const mdb_grid_metrics &metrics,
+                 mdb_grid_result **out);
 struct TimeRangeArg { // (TimeRange of mdb_segment_dev.hpp, for translation units that have no device code)
     int64_t lo;
     int64_t hi;

@@ -26,9 +26,11 @@
 //                         all (only then is it rebuilt). Scan -> output offsets, one read-back sizes the output.
 //   k_mask_write_runs     1 wave / segment: the selected model points start + k * delta, compacted 64 rows at a time
 //                         with __popcll of the mask window (an all-zero window is skipped).
-//   k_mask_points_write   the selected rows of the rebuilt slices, compacted with ballots as k_filter_points does.
-//   k_agg_mask            (mdb_agg.hip) the masked aggregates: segment_rows of mdb_mask.hpp in k_agg_filter's loop and
-//                         fixed reduction tree.
+//   k_mask_points_write   the selected rows of the rebuilt slices, compacted with ballots as k_filter_points_write does
+//                         (both, and k_mask_points_set, are slice_walk of mdb_filter_points.hpp with their own test
+//                         and sink).
+//   k_agg_mask            (mdb_agg.hip) the masked aggregates: k_agg_filter's loop and fixed reduction tree with the
+//                         selector SegmentRows of mdb_mask.hpp in segment_range.
 // All writes are ordinary vector stores; the only atomics are integer ones.
 #include "mdb_filter_points.hpp"
 #include "mdb_host_side.hpp"
@@ -45,11 +47,7 @@
 namespace mdb {
 
 constexpr int MASK_THREADS = 256;
-
-struct MaskRows { // (scan functor: rows per segment)
-    const uint32_t *rows;
-    __device__ uint64_t operator()(uint64_t i) const { return rows[i]; }
-};
+static_assert(MASK_THREADS == FILTER_THREADS, "slice_walk's waves are counted in FILTER_THREADS");
 
 // Adds `local` of every thread of the block to *counter: LDS first, then one integer atomic per block.
 __device__ __forceinline__ void block_count_add(unsigned long long local, unsigned long long *lds,
@@ -118,32 +116,26 @@ __global__ __launch_bounds__(MASK_THREADS) void k_mask_classify(DevSegments s, i
     }
 }
 
-// Producer, one wave per per-point segment of a slice (rows [first[j], first[j + 1]) of the slice's range grid,
-// gathered segment j0 + j): the rows behind the first skip ones whose value passes become ones.
+// Producer, the per-point segments of a slice (slice_walk, mdb_filter_points.hpp): the rows whose value passes become
+// ones - lane 0 ORs the round's ballot into the two words its 64 rows reach into.
 __global__ __launch_bounds__(MASK_THREADS) void k_mask_points_set(const float *__restrict__ slice_val,
                                                                   const unsigned long long *__restrict__ first,
                                                                   uint64_t n_slice, uint64_t j0, Gathered g, ValueKeys keys,
                                                                   const unsigned long long *__restrict__ first_row,
                                                                   unsigned long long *__restrict__ mask, uint64_t n_words) {
-    const uint32_t lane = threadIdx.x & (MDB_WAVE - 1);
-    const uint64_t waves = (uint64_t)gridDim.x * (MASK_THREADS / MDB_WAVE);
-    for (uint64_t j = (uint64_t)blockIdx.x * (MASK_THREADS / MDB_WAVE) + threadIdx.x / MDB_WAVE; j < n_slice; j += waves) {
-        const uint64_t begin = first[j], end = first[j + 1];
-        const uint64_t segment_row = first_row[g.origin[j0 + j]];
-        for (uint64_t row0 = begin + g.skip[j0 + j]; row0 < end; row0 += MDB_WAVE) {
-            const uint64_t row = row0 + lane;
-            const bool in = row < end;
-            const float v = in ? slice_val[row] : 0.0f;
-            const unsigned long long bits = __ballot(in && keys.pass(v));
-            if (lane == 0 && bits != 0) {
-                const uint64_t r = segment_row + (row0 - begin);
-                const uint32_t shift = (uint32_t)(r & 63);
-                const uint64_t w = r >> 6; // (below n_words, as every row of a segment is: never a word beyond the mask)
-                if (w < n_words) atomicOr(&mask[w], bits << shift);
-                if (shift != 0 && (bits >> (64 - shift)) != 0 && w + 1 < n_words) atomicOr(&mask[w + 1], bits >> (64 - shift));
-            }
-        }
-    }
+    slice_walk(first, n_slice, j0, g, [&](uint32_t, uint64_t) { return [&](uint64_t row) { return keys.pass(slice_val[row]); }; },
+               [&](uint32_t origin, uint64_t begin) {
+                   const uint64_t segment_row = first_row[origin];
+                   return [&, segment_row, begin](uint64_t row0, uint64_t row, bool, unsigned long long bits, uint64_t) {
+                       if (row != row0 || bits == 0) return; // (lane 0)
+                       const uint64_t r = segment_row + (row0 - begin);
+                       const uint32_t shift = (uint32_t)(r & 63);
+                       const uint64_t w = r >> 6; // (below n_words, as every row of a segment is: never a word beyond the mask)
+                       if (w < n_words) atomicOr(&mask[w], bits << shift);
+                       if (shift != 0 && (bits >> (64 - shift)) != 0 && w + 1 < n_words) atomicOr(&mask[w + 1], bits >> (64 - shift));
+                   };
+               },
+               [](uint32_t, uint64_t) {});
 }
 
 __global__ __launch_bounds__(MASK_THREADS) void k_mask_count(const unsigned long long *__restrict__ mask, uint64_t n_words,
@@ -228,52 +220,39 @@ __global__ __launch_bounds__(MASK_THREADS) void k_mask_write_runs(const FilterRu
             if (w == 0) continue;
             if ((w >> lane) & 1ull) {
                 const uint64_t at = base + kept + (uint64_t)__popcll(w & below);
-                const int64_t t = r.start + (int64_t)((uint64_t)(k0 + lane) * (uint64_t)r.delta);
+                int64_t t;
+                float v;
+                run_point(r, k0 + lane, &t, &v);
                 if (out_ts) out_ts[at] = t;
-                out_val[at] = r.type == MDB_SWING_ID ? (float)(r.slope * (double)t + r.intercept) : r.value;
+                out_val[at] = v;
             }
             kept += (uint64_t)__popcll(w);
         }
     }
 }
 
-// One wave per per-point segment of a slice: its selected rows behind the first skip ones, in order, behind the
+// The per-point segments of a slice (slice_walk): their selected rows behind the first skip ones, in order, behind the
 // segment's selected model rows. out_ts may be nullptr.
 __global__ __launch_bounds__(MASK_THREADS) void k_mask_points_write(
     const int64_t *__restrict__ slice_ts, const float *__restrict__ slice_val, const unsigned long long *__restrict__ first,
     uint64_t n_slice, uint64_t j0, Gathered g, const unsigned long long *__restrict__ first_row, RowBits bits,
     const uint32_t *__restrict__ model_sel, const unsigned long long *__restrict__ offsets, int64_t *__restrict__ out_ts,
     float *__restrict__ out_val) {
-    const uint32_t lane = threadIdx.x & (MDB_WAVE - 1);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    const uint64_t waves = (uint64_t)gridDim.x * (MASK_THREADS / MDB_WAVE);
-    for (uint64_t j = (uint64_t)blockIdx.x * (MASK_THREADS / MDB_WAVE) + threadIdx.x / MDB_WAVE; j < n_slice; j += waves) {
-        const uint32_t origin = g.origin[j0 + j];
-        const uint64_t begin = first[j], end = first[j + 1];
-        const uint64_t segment_row = first_row[origin];
-        const uint64_t out = offsets[origin] + model_sel[origin];
-        uint64_t kept = 0;
-        for (uint64_t row0 = begin + g.skip[j0 + j]; row0 < end; row0 += MDB_WAVE) {
-            const uint64_t row = row0 + lane;
-            const bool pass = row < end && bits.test(segment_row + (row - begin));
-            const unsigned long long ballot = __ballot(pass);
-            if (pass) {
-                const uint64_t at = out + kept + (uint64_t)__popcll(ballot & below);
-                if (out_ts) out_ts[at] = slice_ts[row];
-                out_val[at] = slice_val[row];
-            }
-            kept += (uint64_t)__popcll(ballot);
-        }
-    }
+    slice_walk(first, n_slice, j0, g,
+               [&](uint32_t origin, uint64_t begin) {
+                   const uint64_t segment_row = first_row[origin];
+                   return [&, segment_row, begin](uint64_t row) { return bits.test(segment_row + (row - begin)); };
+               },
+               [&](uint32_t origin, uint64_t) {
+                   const uint64_t out = offsets[origin] + model_sel[origin];
+                   return [&, out](uint64_t, uint64_t row, bool pass, unsigned long long ballot, uint64_t kept) {
+                       slice_write_row(out + kept, row, pass, ballot, slice_ts, slice_val, out_ts, out_val);
+                   };
+               },
+               [](uint32_t, uint64_t) {});
 }
 
 namespace {
-
-int fold_keys(const mdb_value_filter *filter, ValueKeys *keys) {
-    if (!value_keys_fold(*filter, keys))
-        return fail("The value filter has unknown flag bits or a reserved field that is not 0.");
-    return 0;
-}
 
 uint64_t words_of(uint64_t n_rows) { return n_rows / 64 + (n_rows % 64 != 0 ? 1 : 0); }
 
@@ -296,22 +275,17 @@ int mask_scratch(mdb_ctx *ctx, uint64_t n, MaskScratch *m) {
     const uint64_t sums = align_up(scan_block_sums_bytes(n), 256);
     void *p = nullptr;
     if (scratch_reserve(ctx, SCRATCH_MASK_SEGMENTS, 4 * b4 + 3 * b8 + runs + sums + 256, &p)) return 1;
-    uint8_t *at = static_cast<uint8_t *>(p);
-    auto take = [&at](uint64_t bytes) {
-        uint8_t *here = at;
-        at += bytes;
-        return here;
-    };
-    m->runs = reinterpret_cast<FilterRun *>(take(runs));
-    m->first_row = reinterpret_cast<unsigned long long *>(take(b8));
-    m->position = reinterpret_cast<unsigned long long *>(take(b8));
-    m->offsets = reinterpret_cast<unsigned long long *>(take(b8));
-    m->block_sums = reinterpret_cast<unsigned long long *>(take(sums));
-    m->words = reinterpret_cast<unsigned long long *>(take(256));
-    m->rows = reinterpret_cast<uint32_t *>(take(b4));
-    m->per_point = reinterpret_cast<uint32_t *>(take(b4));
-    m->counts = reinterpret_cast<uint32_t *>(take(b4));
-    m->model_sel = reinterpret_cast<uint32_t *>(take(b4));
+    Carver scratch(p);
+    m->runs = scratch.take<FilterRun>(n);
+    m->first_row = scratch.take<unsigned long long>(n + 1);
+    m->position = scratch.take<unsigned long long>(n + 1);
+    m->offsets = scratch.take<unsigned long long>(n + 1);
+    m->block_sums = scratch.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
+    m->words = scratch.take<unsigned long long>(4);
+    m->rows = scratch.take<uint32_t>(n);
+    m->per_point = scratch.take<uint32_t>(n);
+    m->counts = scratch.take<uint32_t>(n);
+    m->model_sel = scratch.take<uint32_t>(n);
     return 0;
 }
 
@@ -323,11 +297,7 @@ int rows_plan(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, 
     if (mask_scratch(ctx, in->n, m)) return 1;
     if (grid_range_plan(ctx, in, t_lo, t_hi, total, metrics, m->rows)) return 1;
     if (in->n == 0) return 0;
-    return device_exclusive_scan(ctx, MaskRows{m->rows}, in->n, m->first_row, m->block_sums, "k_mask_scan");
-}
-
-uint32_t wave_blocks(uint64_t n, uint32_t most) {
-    return (uint32_t)std::min<uint64_t>((n + MASK_THREADS / MDB_WAVE - 1) / (MASK_THREADS / MDB_WAVE), most);
+    return device_exclusive_scan(ctx, ItemsOf<uint32_t>{m->rows}, in->n, m->first_row, m->block_sums, "k_mask_scan");
 }
 
 int count_bits(mdb_ctx *ctx, const unsigned long long *mask, uint64_t n_words, unsigned long long *counter, uint64_t *n_set) {
@@ -376,14 +346,12 @@ int mask_filter_locked(mdb_ctx *ctx, const mdb_segments *in, const ValueKeys &ke
         f.t_lo = t_lo;
         f.t_hi = t_hi;
         f.keys = keys;
-        if (filter_gather_tested(ctx, f, m.per_point, m.position, m.block_sums)) return 1;
-        for (const auto &range : f.slices) {
-            if (filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
-            const uint64_t n_slice = range.second - range.first;
-            LaunchTimer timer(ctx, "k_mask_points_set");
-            hipLaunchKernelGGL(k_mask_points_set, dim3(wave_blocks(n_slice, 8192)), dim3(MASK_THREADS), 0, ctx->stream,
-                               f.slice_val, f.slice_first, n_slice, range.first, f.g, keys, m.first_row, mask, n_words);
-        }
+        if (filter_tested_slices(ctx, f, m.per_point, m.position, m.block_sums, [&](uint64_t j0, uint64_t n_slice) {
+                LaunchTimer timer(ctx, "k_mask_points_set");
+                hipLaunchKernelGGL(k_mask_points_set, dim3(slice_walk_blocks(n_slice, 8192)), dim3(MASK_THREADS), 0, ctx->stream,
+                                   f.slice_val, f.slice_first, n_slice, j0, f.g, keys, m.first_row, mask, n_words);
+            }))
+            return 1;
         if (n_set && count_bits(ctx, mask, n_words, m.words + 3, &set)) return 1;
     }
     MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -456,17 +424,7 @@ int mask_grid_count(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t 
                            ctx->stream, to_dev(in), t_lo, t_hi, g.m.rows, g.m.first_row, g.bits, g.m.runs, g.m.per_point,
                            g.m.counts, g.m.model_sel);
     }
-    if (device_exclusive_scan(ctx, MaskRows{g.m.counts}, n, g.m.offsets, g.m.block_sums, "k_mask_scan")) return 1;
-    if (filter_rows_by_type(ctx, in->model_type_id, g.m.counts, n, g.m.words)) return 1;
-    unsigned long long words[4] = {0, 0, 0, 0};
-    MDB_HIP_CHECK(hipMemcpyAsync(&words[0], g.m.offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipMemcpyAsync(&words[1], g.m.words, 3 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    g.total = words[0];
-    g.metrics.rows_created = g.total;
-    for (int k = 0; k < 3; k++) g.metrics.rows_created_by_model_type[k] = words[1 + k];
-    return 0;
+    return filter_count_done(ctx, in, g.m.counts, g.m.offsets, g.m.block_sums, g.m.words, "k_mask_scan", &g.total, &g.metrics);
 }
 
 // Pass 2: the rows into out_ts (may be nullptr) / out_val, rows per segment into out_rows (may be nullptr).
@@ -476,22 +434,20 @@ int mask_grid_write(mdb_ctx *ctx, MaskGridPass &g, int64_t *out_ts, float *out_v
     if (g.total > 0) {
         {
             LaunchTimer timer(ctx, "k_mask_write_runs");
-            hipLaunchKernelGGL(k_mask_write_runs, dim3(wave_blocks(n, 16384)), dim3(MASK_THREADS), 0, ctx->stream, g.m.runs, n,
+            hipLaunchKernelGGL(k_mask_write_runs, dim3(slice_walk_blocks(n, 16384)), dim3(MASK_THREADS), 0, ctx->stream, g.m.runs, n,
                                g.m.first_row, g.bits, g.m.model_sel, g.m.offsets, out_ts, out_val);
         }
         FilterPass f;
         f.in = g.in;
         f.t_lo = g.t_lo;
         f.t_hi = g.t_hi;
-        if (filter_gather_tested(ctx, f, g.m.per_point, g.m.position, g.m.block_sums)) return 1;
-        for (const auto &range : f.slices) {
-            if (filter_rebuild_slice(ctx, f, range.first, range.second)) return 1;
-            const uint64_t n_slice = range.second - range.first;
-            LaunchTimer timer(ctx, "k_mask_points_write");
-            hipLaunchKernelGGL(k_mask_points_write, dim3(wave_blocks(n_slice, 8192)), dim3(MASK_THREADS), 0, ctx->stream,
-                               f.slice_ts, f.slice_val, f.slice_first, n_slice, range.first, f.g, g.m.first_row, g.bits,
-                               g.m.model_sel, g.m.offsets, out_ts, out_val);
-        }
+        if (filter_tested_slices(ctx, f, g.m.per_point, g.m.position, g.m.block_sums, [&](uint64_t j0, uint64_t n_slice) {
+                LaunchTimer timer(ctx, "k_mask_points_write");
+                hipLaunchKernelGGL(k_mask_points_write, dim3(slice_walk_blocks(n_slice, 8192)), dim3(MASK_THREADS), 0, ctx->stream,
+                                   f.slice_ts, f.slice_val, f.slice_first, n_slice, j0, f.g, g.m.first_row, g.bits,
+                                   g.m.model_sel, g.m.offsets, out_ts, out_val);
+            }))
+            return 1;
     }
     if (out_rows) MDB_HIP_CHECK(hipMemcpyAsync(out_rows, g.m.counts, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
@@ -541,7 +497,7 @@ int where_check(const mdb_segments *const *pred_fields, const mdb_value_filter *
     w->keys.resize(n_preds);
     for (uint32_t k = 0; k < n_preds; k++) {
         if (!pred_fields[k]) return fail("A batch of pred_fields is NULL.");
-        if (fold_keys(&filters[k], &w->keys[k])) return 1;
+        if (value_keys_fold(&filters[k], &w->keys[k])) return 1;
         w->t_lo = std::max(w->t_lo, filters[k].t_lo);
         w->t_hi = std::min(w->t_hi, filters[k].t_hi);
     }
@@ -575,39 +531,6 @@ int where_mask(mdb_ctx *ctx, const mdb_segments *const *pred_fields, uint32_t n_
     return 0;
 }
 
-// A result block of n rows (n_segments rows_per_segment) copied from the device staging area `stage` (the same gaps).
-int owned_result(mdb_ctx *ctx, const void *stage, uint64_t ts_bytes, uint64_t val_bytes, uint64_t rows_bytes, uint64_t front,
-                 uint64_t n, uint64_t n_segments, bool values_only, const mdb_grid_metrics &metrics, mdb_grid_result **out) {
-    void *block = nullptr;
-    uint64_t capacity = 0;
-    const uint64_t bytes = ts_bytes + val_bytes + rows_bytes;
-    if (ctx->pinned_pool->take(bytes, &block, &capacity)) return 1;
-    if (stage) {
-        if (hipMemcpyAsync(block, stage, bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            ctx->pinned_pool->give(block, capacity);
-            return fail("hipMemcpy device to host failed.");
-        }
-    } else {
-        std::memset(static_cast<uint8_t *>(block) + ts_bytes + val_bytes, 0, rows_bytes);
-    }
-    OwnedGridResult *result = new OwnedGridResult();
-    uint8_t *host = static_cast<uint8_t *>(block);
-    result->c.timestamps = values_only ? nullptr : reinterpret_cast<int64_t *>(host) + front;
-    result->c.values = reinterpret_cast<float *>(host + ts_bytes) + front;
-    result->c.rows_per_segment = reinterpret_cast<uint32_t *>(host + ts_bytes + val_bytes);
-    result->c.n = n;
-    result->c.n_segments = n_segments;
-    result->c.reserved_front = front;
-    result->c.metrics = metrics;
-    result->c.priv_ = result;
-    result->pool = ctx->pinned_pool;
-    result->block = block;
-    result->capacity = capacity;
-    *out = &result->c;
-    return 0;
-}
-
 } // namespace
 
 } // namespace mdb
@@ -620,7 +543,7 @@ int mdb_mask_filter_dev(mdb_ctx *ctx, const mdb_segments *in, const mdb_value_fi
                         uint64_t cap_words, uint64_t *n_rows, uint64_t *n_set) {
     if (!ctx || !in || !filter || !n_rows) return fail("ctx, in, filter and n_rows must not be NULL.");
     ValueKeys keys;
-    if (fold_keys(filter, &keys)) return 1;
+    if (value_keys_fold(filter, &keys)) return 1;
     mdb::CallGuard lock(ctx);
     MDB_HIP_CHECK(hipSetDevice(ctx->device));
     uint64_t rows = 0, set = 0;
@@ -700,14 +623,10 @@ int mdb_grid_batch_where_owned(mdb_ctx *ctx, const mdb_segments *const *pred_fie
     Where w;
     if (where_check(pred_fields, filters, n_preds, &w)) return 1;
     const bool values_only = (flags & MDB_GRID_VALUES_ONLY) != 0;
-    const uint64_t front = align_up(reserve_front, 4);
-    const uint64_t rows_bytes = align_up(target->n * 4, 256);
     mdb::CallGuard lock(ctx);
     MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    if (w.t_lo > w.t_hi) { // an empty intersection of the time ranges selects nothing
-        const uint64_t ts_bytes = values_only ? 0 : align_up(front * 8, 256), val_bytes = align_up(front * 4, 256);
-        return owned_result(ctx, nullptr, ts_bytes, val_bytes, rows_bytes, front, 0, target->n, values_only, mdb_grid_metrics{}, out);
-    }
+    if (w.t_lo > w.t_hi) // an empty intersection of the time ranges selects nothing
+        return owned_result(ctx, nullptr, result_layout(reserve_front, 0, target->n, values_only), mdb_grid_metrics{}, out);
     Uploads uploads;
     const mdb_segments *target_dev = nullptr;
     if (uploads.get(ctx, target, &target_dev)) return 1;
@@ -716,18 +635,12 @@ int mdb_grid_batch_where_owned(mdb_ctx *ctx, const mdb_segments *const *pred_fie
     if (where_mask(ctx, pred_fields, n_preds, w, uploads, target_dev, &mask, &n_rows)) return 1;
     MaskGridPass g;
     if (mask_grid_count(ctx, target_dev, w.t_lo, w.t_hi, mask, n_rows, g)) return 1;
-    // The device staging area mirrors the host block (same gaps), so one copy moves it all.
-    const uint64_t ts_bytes = values_only ? 0 : align_up((front + g.total) * 8, 256);
-    const uint64_t val_bytes = align_up((front + g.total) * 4, 256);
+    const ResultLayout layout = result_layout(reserve_front, g.total, target->n, values_only);
     void *stage = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_STAGE_DEV, ts_bytes + val_bytes + rows_bytes, &stage)) return 1;
-    uint8_t *base = static_cast<uint8_t *>(stage);
-    uint32_t *stage_rows = reinterpret_cast<uint32_t *>(base + ts_bytes + val_bytes);
-    if (target->n == 0) MDB_HIP_CHECK(hipMemsetAsync(stage_rows, 0, rows_bytes, ctx->stream));
-    if (mask_grid_write(ctx, g, values_only ? nullptr : reinterpret_cast<int64_t *>(base) + front,
-                        reinterpret_cast<float *>(base + ts_bytes) + front, stage_rows))
-        return 1;
-    return owned_result(ctx, stage, ts_bytes, val_bytes, rows_bytes, front, g.total, target->n, values_only, g.metrics, out);
+    if (scratch_reserve(ctx, SCRATCH_STAGE_DEV, layout.bytes(), &stage)) return 1;
+    if (target->n == 0) MDB_HIP_CHECK(hipMemsetAsync(layout.rows(stage), 0, layout.rows_bytes, ctx->stream));
+    if (mask_grid_write(ctx, g, layout.timestamps(stage), layout.values(stage), layout.rows(stage))) return 1;
+    return owned_result(ctx, stage, layout, g.metrics, out);
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
-// mdb_mask.hpp - row masks on the device: the bits of a mask (RowBits) and the points of one segment that a mask
-// selects, aggregated without materialising them (segment_rows: segment_range of mdb_agg_dev.hpp with a predicate
-// that sees the ROW of a point instead of its value). Shared by mdb_mask.hip and the masked aggregate of mdb_agg.hip.
+// mdb_mask.hpp - row masks on the device: the bits of a mask (RowBits), what a mask selects of a model's points
+// (model_rows), and the two as a selector of segment_range (SegmentRows: mdb_agg_dev.hpp's walk with a test of the ROW
+// of a point instead of its value). Shared by mdb_mask.hip and the masked aggregate of mdb_agg.hip.
 //
 // A mask over n_rows rows is ceil(n_rows / 64) 64-bit words; row r is bit r % 64 of word r / 64 (on a little-endian
 // host an Arrow boolean bitmap byte for byte), bits at and beyond n_rows are zero. The rows are those of the range
@@ -78,93 +78,18 @@ __device__ __forceinline__ void model_rows(const SegDesc &d, uint32_t type, uint
     if (run_n != 0) model_closed_form(d, type, run_a, run_a + run_n - 1, acc);
 }
 
-// Aggregate the points of segment i whose timestamp lies in [t_lo, t_hi] and whose row is set in `bits`; the
-// segment's first point inside the range is row `first_row`. The passes over the streams are segment_range's.
-__device__ __forceinline__ void segment_rows(const DevSegments &s, uint64_t i, const SegInfo &info, int64_t t_lo,
-                                             int64_t t_hi, uint64_t first_row, const RowBits &bits, RangeAcc &acc,
-                                             uint32_t *error) {
-    const SegDesc &d = info.desc;
-    const uint32_t type = d.flags & FLAG_TYPE_MASK;
-    const int64_t end = s.end_time[i];
-    const uint32_t n_res = d.n_total - d.n_model;
-    if (!(d.flags & FLAG_REGULAR)) {
-        if (end < t_lo || d.start > t_hi) return;
-        const uint4 vt = s.timestamps.views[i];
-        const uint8_t *ts_bytes = view_data(s.timestamps, i, vt);
-        if (type != MDB_MACAQUE_V_ID && n_res == 0) {
-            uint64_t row = first_row;
-            decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error, [&](uint32_t, int64_t t) {
-                if (t >= t_lo && t <= t_hi) {
-                    if (bits.test(row)) acc.point(model_value_at(d, type, t));
-                    row += 1;
-                }
-            });
-            return;
-        }
-        // The index interval of the in-range timestamps first (they are sorted), then the values once.
-        uint32_t k_lo = 0xffffffffu, k_hi = 0;
-        decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, 0xffffffffu, error, [&](uint32_t k, int64_t t) {
-            if (t >= t_lo && t <= t_hi) {
-                if (k < k_lo) k_lo = k;
-                if (k > k_hi) k_hi = k;
-            }
-        });
-        if (k_lo == 0xffffffffu) return;
-        auto selected = [&](uint32_t k) { return k >= k_lo && k <= k_hi && bits.test(first_row + (k - k_lo)); };
-        float seed = d.value;
-        if (type == MDB_MACAQUE_V_ID) {
-            const uint4 vv = s.values.views[i];
-            uint32_t last_bits = 0;
-            decode_macaque_v(view_data(s.values, i, vv), vv.x, d.n_model, false, 0, error, [&](uint32_t k, uint32_t v) {
-                if (selected(k)) acc.point(__uint_as_float(v));
-                last_bits = v;
-            });
-            seed = __uint_as_float(last_bits);
-        } else {
-            decode_irregular_timestamps(ts_bytes, vt.x, d.start, end, d.n_model, error, [&](uint32_t k, int64_t t) {
-                if (selected(k)) acc.point(model_value_at(d, type, t));
-            });
-        }
-        if (n_res > 0) {
-            const uint4 vr = s.residuals.views[i];
-            decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, n_res, true, __float_as_uint(seed), error,
-                             [&](uint32_t k, uint32_t v) {
-                                 if (selected(d.n_model + k)) acc.point(__uint_as_float(v));
-                             });
-        }
-        return;
+// The selector of segment_range (mdb_agg_dev.hpp) for a mask: the segment's first point inside the range is row
+// `first_row` of `bits`, a point counts when its row is set.
+struct SegmentRows {
+    static constexpr bool by_row = true;
+    RowBits bits;
+    uint64_t first_row;
+    __device__ __forceinline__ bool counts(float, uint64_t row) const { return bits.test(first_row + row); }
+    __device__ __forceinline__ void model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t row_a,
+                                          RangeAcc &acc) const {
+        model_rows(d, type, a, b, first_row + row_a, bits, acc);
     }
-
-    // Regular timestamps start + k * delta: the in-range indices are an interval [k_lo, k_hi]; point k is row
-    // first_row + (k - k_lo).
-    uint32_t k_lo = 0, k_hi = 0;
-    if (!regular_index_interval(d.start, d.delta, d.n_total, t_lo, t_hi, &k_lo, &k_hi)) return;
-    auto selected = [&](uint32_t k) { return k >= k_lo && k <= k_hi && bits.test(first_row + (k - k_lo)); };
-    if (type != MDB_MACAQUE_V_ID && k_lo < d.n_model) model_rows(d, type, k_lo, min(k_hi, d.n_model - 1), first_row, bits, acc);
-    float seed = d.value;
-    if (type == MDB_MACAQUE_V_ID) {
-        const uint4 vv = s.values.views[i];
-        uint32_t last_bits = 0;
-        // Decode only as far as needed unless the residual seed (last value) is needed too.
-        const bool residuals_in_range = n_res > 0 && k_hi >= d.n_model;
-        const uint32_t upto = residuals_in_range ? d.n_model : min(d.n_model, k_hi + 1);
-        if (k_lo < d.n_model || residuals_in_range) {
-            decode_macaque_v(view_data(s.values, i, vv), vv.x, upto, false, 0, error, [&](uint32_t k, uint32_t v) {
-                if (selected(k)) acc.point(__uint_as_float(v));
-                last_bits = v;
-            });
-        }
-        seed = __uint_as_float(last_bits);
-    }
-    if (n_res > 0 && k_hi >= d.n_model) {
-        const uint4 vr = s.residuals.views[i];
-        const uint32_t upto = k_hi - d.n_model + 1;
-        decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, upto, true, __float_as_uint(seed), error,
-                         [&](uint32_t k, uint32_t v) {
-                             if (selected(d.n_model + k)) acc.point(__uint_as_float(v));
-                         });
-    }
-}
+};
 
 // mdb_agg.hip: the points of a batch in HBM that `words` selects (n_words words in HBM; first_row: n entries in HBM)
 // folded into *inout with the rules of agg_filter_run (the lock held, the device set).

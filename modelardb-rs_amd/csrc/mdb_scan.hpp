@@ -11,6 +11,13 @@ constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 4;
 constexpr int SCAN_BLOCK_ITEMS = SCAN_THREADS * SCAN_ITEMS;
 
+// The functor of an array: f(i) = items[i] (rows per segment, pairs per segment, ...).
+template <typename T>
+struct ItemsOf {
+    const T *items;
+    __device__ uint64_t operator()(uint64_t i) const { return items[i]; }
+};
+
 template <typename F>
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_reduce(F f, uint64_t n,
                                                              unsigned long long *__restrict__ block_sums) {
