@@ -382,6 +382,55 @@ int mdb_grid_batch_where_owned(mdb_ctx *ctx, const mdb_segments *const *pred_fie
                                uint32_t n_preds, const mdb_segments *target, uint32_t flags, uint64_t reserve_front,
                                mdb_grid_result **out);
 
+/* Extension: value histograms and exact quantiles -
+ *   SELECT approx_percentile_cont(field, 0.95) ... / SELECT median(field) ... WHERE ts BETWEEN ... / a histogram of a
+ *   field per series,
+ * which the reference answers with GridExec -> AggregateExec (approx_percentile_cont / median are not among the
+ * aggregates its model-based rule rewrites, optimizer/model_simple_aggregates.rs: every point is rebuilt first). Here
+ * the points are counted per cell on the segments: a PMC-Mean segment is one addition, a Swing segment on regular
+ * timestamps one binary search over its point index per edge it crosses, a bit stream is decoded once.
+ *   Cells: mdb_hist_request (mdb_format.h): n_cells = n_edges + 1, a point of value v in cell c = the number of edges
+ *     e with key(e) <= key(v) in the totalOrder of mdb_value_filter (-0.0 lies below an edge at +0.0, a NaN lands
+ *     where its key puts it).
+ *   counts: uint64_t [n_groups][n_cells], row-major. A call ADDS the batch's points - exactly the rows of
+ *     mdb_grid_batch_range(in, t_lo, t_hi), segment row i in group group_of_segment[i] (NULL: every segment in group 0) -
+ *     to them; a fresh histogram is all zeros, a cell that receives nothing is left as it was. Per group the cells'
+ *     increments add up to the COUNT of mdb_agg_buckets with one bucket over [t_lo, t_hi]; the increments of cells
+ *     a + 1 .. b to the COUNT of mdb_agg_batch_filter with [edges[a], edges[b]).
+ *   Determinism: integers only (integer atomics on zeroed scratch cells, folded into counts once the pass has
+ *     finished): the three forms and any two runs agree bit for bit.
+ *   Errors (mdb_last_error set, counts untouched): a NULL argument; flags or reserved != 0, n_edges outside
+ *     1 .. MDB_HIST_MAX_EDGES, edges not strictly increasing in totalOrder (equal keys, descending, -0.0 after +0.0),
+ *     n_groups == 0 (all checked before the device is used); n_groups * n_cells counters that do not fit the device; a
+ *     group id >= n_groups on ANY row, also one outside the time range; the malformed-segment classes of
+ *     mdb_agg_batch_range. An empty batch or an empty time range succeeds and changes nothing. */
+int mdb_hist_batch(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                   const mdb_hist_request *request, const float *edges, uint64_t *counts);
+/* The segments, group_of_segment and counts are in HBM; request and edges are host pointers. */
+int mdb_hist_batch_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                       const mdb_hist_request *request, const float *edges, uint64_t *counts);
+/* Several host batches (rows in the order of the list) counted as one batch; group_of_segment[k] (or NULL) per batch. */
+int mdb_hist_batch_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                        uint32_t n_inputs, const mdb_hist_request *request, const float *edges, uint64_t *counts);
+/* Order statistics of the points inside [t_lo, t_hi] of the whole batch, in totalOrder, exact (what DataFusion's
+ * median / percentile_cont compute from the rebuilt points; approx_percentile_cont approximates the same).
+ * For q[i] in [0, 1]: p = q[i] * (double)(N - 1), out_lo[i] = the floor(p)-th smallest point (0-based), out_hi[i] =
+ * the ceil(p)-th; *n_points = N. N == 0: succeeds, *n_points = 0, out_lo / out_hi untouched. 1 <= n_q <= 16.
+ * The batch is uploaded once; the ranks are pinned by repeated histogram passes over the resident copy (edges even in
+ * key space, then inside the cell that holds the rank: 12 + 12 + 8 bits, three passes for ranks that share their
+ * cells). Interpolation (lo + (hi - lo) * fraction, mdb_quantile_positions) is the caller's.
+ * Errors (outputs untouched): a NULL argument, q outside [0, 1] or NaN, n_q out of range, a malformed segment. */
+int mdb_quantile_batch(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const double *q, uint32_t n_q,
+                       float *out_lo, float *out_hi, uint64_t *n_points);
+/* The segments are in HBM. */
+int mdb_quantile_batch_dev(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, const double *q,
+                           uint32_t n_q, float *out_lo, float *out_hi, uint64_t *n_points);
+/* Host arithmetic, no context, no GPU: the cell rule (validates the edges as mdb_hist_batch does) ... */
+int mdb_hist_cell_of(const float *edges, uint32_t n_edges, float value, uint32_t *cell);
+/* ... and the ranks of a quantile: p = q * (double)(n_points - 1), *rank_lo = floor(p), *rank_hi = ceil(p),
+ * *fraction = p - floor(p). Errors: n_points == 0, q outside [0, 1] or NaN, a NULL output. */
+int mdb_quantile_positions(double q, uint64_t n_points, uint64_t *rank_lo, uint64_t *rank_hi, double *fraction);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

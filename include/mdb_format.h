@@ -186,6 +186,19 @@ typedef struct mdb_value_filter {
     uint32_t reserved;     /* must be 0 */
 } mdb_value_filter;        /* 32 bytes */
 
+/* A value histogram for mdb_hist_batch*: n_edges edges (floats in a host array, strictly increasing in the totalOrder of
+ * mdb_value_filter) cut the values into n_edges + 1 cells; a point of value v falls in cell c = the number of edges e
+ * with key(e) <= key(v): cell 0 holds the points below the first edge, cell n_edges the points at or above the last.
+ * 4 095 edges give 4 096 cells: 16 KB of keys in LDS, and three passes of 12 + 12 + 8 bits cover the 32-bit keys. */
+#define MDB_HIST_MAX_EDGES 4095u
+typedef struct mdb_hist_request {
+    int64_t  t_lo, t_hi;   /* inclusive time range (INT64_MIN / INT64_MAX: none) */
+    uint32_t n_edges;      /* 1 .. MDB_HIST_MAX_EDGES */
+    uint32_t n_groups;     /* >= 1 */
+    uint32_t flags;        /* must be 0 */
+    uint32_t reserved;     /* must be 0 */
+} mdb_hist_request;        /* 32 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -269,5 +282,11 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, v_lo) == 16);
 MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, v_hi) == 20);
 MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, flags) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_value_filter, reserved) == 28);
+MDB_LAYOUT_ASSERT(sizeof(mdb_hist_request) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, t_hi) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, n_edges) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, n_groups) == 20);
+MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, flags) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, reserved) == 28);
 
 #endif /* MDB_FORMAT_H */

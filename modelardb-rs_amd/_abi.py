@@ -182,6 +182,20 @@ class ValueFilterC(C.Structure):
     ]
 
 
+class HistRequestC(C.Structure):
+    """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
+    _fields_ = [
+        ("t_lo", C.c_int64),
+        ("t_hi", C.c_int64),
+        ("n_edges", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+MDB_HIST_MAX_EDGES = 4095
+
 _HIP_SYMBOLS = {
     # name: (restype, argtypes)
     "mdb_init": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
@@ -283,6 +297,19 @@ _HIP_SYMBOLS = {
     "mdb_grid_batch_where_owned": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(ValueFilterC),
                                              C.c_uint32, C.POINTER(SegmentsC), C.c_uint32, C.c_uint64,
                                              C.POINTER(C.POINTER(GridResultC))]),
+    "mdb_hist_batch": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(HistRequestC), C.c_void_p,
+                                 C.c_void_p]),
+    "mdb_hist_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(HistRequestC), C.c_void_p,
+                                     C.c_void_p]),
+    "mdb_hist_batch_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                      C.POINTER(HistRequestC), C.c_void_p, C.c_void_p]),
+    "mdb_quantile_batch": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_int64, C.c_int64, C.c_void_p, C.c_uint32,
+                                     C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mdb_quantile_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_int64, C.c_int64, C.c_void_p, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mdb_hist_cell_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32)]),
+    "mdb_quantile_positions": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_double)]),
     "mdb_compress_series": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, ErrorBoundC,
                                       C.POINTER(C.POINTER(SegmentsOwnedC))]),
     "mdb_compress_chunks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,

@@ -247,6 +247,34 @@ def are_compressed_timestamps_regular(data):
     return bool(regular.value)
 
 
+def _edges_array(edges):
+    edges = np.ascontiguousarray(edges, dtype=np.float32)
+    if edges.ndim != 1:
+        raise ValueError("edges must be a one-dimensional array of float32")
+    return edges
+
+
+def hist_cell_of(edges, value):
+    """The cell of `value` under `edges` (mdb_hist_cell_of: the number of edges at or below it in totalOrder; host
+    arithmetic, no GPU). Raises for edges mdb_hist_batch would reject."""
+    lib = _abi.load_hip_library()
+    edges = _edges_array(edges)
+    cell = C.c_uint32()
+    value = C.c_float.from_buffer_copy(np.asarray(value, dtype=np.float32).tobytes())  # (keeps a NaN's payload)
+    if lib.mdb_hist_cell_of(edges.ctypes.data_as(C.c_void_p), len(edges), value, C.byref(cell)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return cell.value
+
+
+def quantile_positions(q, n_points):
+    """(rank_lo, rank_hi, fraction) of quantile q over n_points points (mdb_quantile_positions; host arithmetic)."""
+    lib = _abi.load_hip_library()
+    rank_lo, rank_hi, fraction = C.c_uint64(), C.c_uint64(), C.c_double()
+    if lib.mdb_quantile_positions(float(q), int(n_points), C.byref(rank_lo), C.byref(rank_hi), C.byref(fraction)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return rank_lo.value, rank_hi.value, fraction.value
+
+
 class Context:
     def __init__(self, device=0):
         self.lib = _abi.load_hip_library()
@@ -837,6 +865,95 @@ class Context:
         if states is not None:
             return int(states.shape[0])
         return max([int(g.max()) + 1 for g in groups if g is not None and g.size] or [1])
+
+    # ---- value histograms and quantiles ------------------------------------------------------------
+
+    @staticmethod
+    def _hist_request(edges, n_groups, t_lo, t_hi):
+        return _abi.HistRequestC(INT64_MIN if t_lo is None else int(t_lo), INT64_MAX if t_hi is None else int(t_hi),
+                                 len(edges), int(n_groups), 0, 0)
+
+    @staticmethod
+    def _hist_counts(counts, n_groups, n_cells):
+        if counts is None:
+            return np.zeros((n_groups, n_cells), dtype=np.uint64)
+        if counts.dtype != np.uint64 or counts.shape != (n_groups, n_cells) or not counts.flags.c_contiguous:
+            raise ValueError(f"counts must be a contiguous ({n_groups}, {n_cells}) array of uint64")
+        return counts
+
+    def hist(self, batch, edges, groups=None, t_lo=None, t_hi=None, counts=None, n_groups=None):
+        """The points of `batch` inside [t_lo, t_hi] ADDED to `counts` (or to fresh zeros), shape (n_groups,
+        len(edges) + 1): cell c of a value = the number of edges at or below it in totalOrder (mdb_hist_batch).
+        `groups`: one id per segment row (None: all in group 0); n_groups defaults to counts' rows, else to
+        max(groups) + 1."""
+        return self.hist_list([batch], edges, None if groups is None else [groups], t_lo, t_hi, counts, n_groups)
+
+    def hist_list(self, batches, edges, groups=None, t_lo=None, t_hi=None, counts=None, n_groups=None):
+        """Several host batches counted as one (mdb_hist_batch_list); `groups`: None or one array (or None) per batch."""
+        edges = _edges_array(edges)
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, counts, batch_groups)
+        counts = self._hist_counts(counts, n_groups, len(edges) + 1)
+        request = self._hist_request(edges, n_groups, t_lo, t_hi)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_hist_batch_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                 edges.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        return counts
+
+    def hist_dev(self, dev_segments, edges, groups=None, t_lo=None, t_hi=None, counts=None, n_groups=None):
+        """mdb_hist_batch_dev on a resident batch: `groups` and `counts` are uploaded, the counts downloaded again."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, counts, [groups])
+        counts = self._hist_counts(counts, n_groups, len(edges) + 1)
+        request = self._hist_request(edges, n_groups, t_lo, t_hi)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_counts = self.upload_array(counts)
+        try:
+            self._check(self.lib.mdb_hist_batch_dev(self.handle, C.byref(dev_segments.seg),
+                                                    None if dev_groups is None else C.c_void_p(dev_groups),
+                                                    C.byref(request), edges.ctypes.data_as(C.c_void_p),
+                                                    C.c_void_p(dev_counts)))
+            counts[...] = self.download_array(dev_counts, counts.size, np.uint64).reshape(counts.shape)
+        finally:
+            self.dev_free(dev_counts)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return counts
+
+    def _quantile(self, call, seg, q, t_lo, t_hi, interpolate):
+        q = np.atleast_1d(np.ascontiguousarray(q, dtype=np.float64))
+        lo = np.full(len(q), np.nan, dtype=np.float32)
+        hi = np.full(len(q), np.nan, dtype=np.float32)
+        n_points = C.c_uint64()
+        self._check(call(self.handle, C.byref(seg), INT64_MIN if t_lo is None else int(t_lo),
+                         INT64_MAX if t_hi is None else int(t_hi), q.ctypes.data_as(C.c_void_p), len(q),
+                         lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), C.byref(n_points)))
+        if not interpolate:
+            return lo, hi, n_points.value
+        if n_points.value == 0:
+            return np.full(len(q), np.nan), 0
+        fractions = np.array([quantile_positions(x, n_points.value)[2] for x in q])
+        wide_lo, wide_hi = lo.astype(np.float64), hi.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            # (equal ends - also infinite ones - are the value itself: no inf - inf)
+            values = np.where(lo.view(np.uint32) == hi.view(np.uint32), wide_lo, wide_lo + (wide_hi - wide_lo) * fractions)
+        return values, n_points.value
+
+    def quantile(self, batch, q, t_lo=None, t_hi=None, interpolate=False):
+        """Exact order statistics of the points of `batch` inside [t_lo, t_hi], in totalOrder (mdb_quantile_batch):
+        (lo, hi, n_points) with lo[i] / hi[i] the floor / ceil ranks of q[i] * (n_points - 1) (NaN-filled when there
+        is no point); interpolate=True: (lo + (hi - lo) * fraction in f64 - DataFusion's percentile_cont, and its
+        median for q = 0.5 - and n_points)."""
+        return self._quantile(self.lib.mdb_quantile_batch, batch.as_c(), q, t_lo, t_hi, interpolate)
+
+    def quantile_dev(self, dev_segments, q, t_lo=None, t_hi=None, interpolate=False):
+        """quantile on a resident batch (mdb_quantile_batch_dev)."""
+        return self._quantile(self.lib.mdb_quantile_batch_dev, dev_segments.seg, q, t_lo, t_hi, interpolate)
 
     # ---- fit -------------------------------------------------------------------------------------
 

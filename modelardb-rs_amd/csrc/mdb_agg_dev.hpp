@@ -290,4 +290,9 @@ int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketReques
                           unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
                           const ValueKeys *filter);
 
+// mdb_buckets.hip: the group ids of host batches (groups[k]: rows[k] ids or nullptr, groups itself may be nullptr) as
+// one device array in the context's scratch (*out nullptr: every segment in group 0).
+int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs, uint64_t n,
+                  const uint32_t **out);
+
 } // namespace mdb

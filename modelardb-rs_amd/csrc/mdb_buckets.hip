@@ -487,8 +487,8 @@ static int bucket_filter_check(const mdb_bucket_request *request, const mdb_valu
     return 0;
 }
 
-// The group ids of the host forms, uploaded next to the batch (nullptr: every segment in group 0).
-static int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs,
+// The group ids of the host forms, uploaded next to the batch (nullptr: every segment in group 0). (mdb_hist.hip too)
+int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs,
                          uint64_t n, const uint32_t **out) {
     *out = nullptr;
     bool any = false;

@@ -94,6 +94,7 @@ enum ScratchSlot {
     SCRATCH_FILTER_SLICE,    // ... one slice of their rebuilt points
     SCRATCH_MASK_SEGMENTS,   // mdb_mask_* / mdb_*_mask*: per segment its rows, first row, class, counts and the scans
     SCRATCH_MASK_WORDS,      // ... the masks of the host forms (mdb_*_where*)
+    SCRATCH_HIST_CELLS,      // mdb_hist_* / mdb_quantile_*: the zeroed cells of one pass, the edges' keys, the error word
     SCRATCH_SLOT_COUNT
 };
 

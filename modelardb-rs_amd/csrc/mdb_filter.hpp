@@ -82,6 +82,24 @@ enum : int { RUN_NONE = 0, RUN_INTERVAL = 1, RUN_POINTS = 2 };
 // direction given by the two ends) and the passing points are one interval, found by two binary searches over k
 // with exact evaluations: at most 2 * ceil(log2(b - a + 2)) evaluations. The stored min_value / max_value are not
 // used: at epoch-scale timestamps the evaluated points can round past them.
+// Point k of a Swing segment with regular timestamps, as grid() rebuilds it.
+__device__ __forceinline__ float swing_value_at(const SegDesc &d, uint32_t k) {
+    const int64_t t = d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta);
+    return (float)(d.slope * (double)t + d.intercept);
+}
+
+// The first k in [lo, hi) whose key is `past` (past is false ... false, true ... true along k, the keys of a Swing
+// segment being sorted; hi if none): a binary search with exact evaluations. Shared with the histograms (mdb_hist.hip).
+template <typename Past>
+__device__ __forceinline__ uint32_t swing_first_past(const SegDesc &d, uint32_t lo, uint32_t hi, const Past &past) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (past(total_order_key(__float_as_uint(swing_value_at(d, mid))))) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+
 template <typename Pred>
 __device__ __forceinline__ int model_run(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, const Pred &pred,
                                          uint32_t *ra, uint32_t *rb) {
@@ -91,11 +109,7 @@ __device__ __forceinline__ int model_run(const SegDesc &d, uint32_t type, uint32
         *rb = b;
         return RUN_INTERVAL;
     }
-    auto value_at = [&](uint32_t k) {
-        const int64_t t = d.start + (int64_t)((uint64_t)k * (uint64_t)d.delta);
-        return (float)(d.slope * (double)t + d.intercept);
-    };
-    const float va = value_at(a), vb = value_at(b);
+    const float va = swing_value_at(d, a), vb = swing_value_at(d, b);
     if (va != va || vb != vb) return RUN_POINTS;
     const int32_t ka = total_order_key(__float_as_uint(va)), kb = total_order_key(__float_as_uint(vb));
     if (pred.key_passes(ka) && pred.key_passes(kb)) {
@@ -106,15 +120,7 @@ __device__ __forceinline__ int model_run(const SegDesc &d, uint32_t type, uint32
     if ((ka < pred.lo && kb < pred.lo) || (ka > pred.hi && kb > pred.hi)) return RUN_NONE;
     const bool up = ka <= kb;
     // The first k in [a, b + 1) for which `past` holds (past is false ... false, true ... true along k).
-    auto first = [&](auto past) {
-        uint32_t lo = a, hi = b + 1;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2;
-            if (past(total_order_key(__float_as_uint(value_at(mid))))) hi = mid;
-            else lo = mid + 1;
-        }
-        return lo;
-    };
+    auto first = [&](auto past) { return swing_first_past(d, a, b + 1, past); };
     const uint32_t s = up ? first([&](int32_t key) { return key >= pred.lo; }) : first([&](int32_t key) { return key <= pred.hi; });
     const uint32_t e = up ? first([&](int32_t key) { return key > pred.hi; }) : first([&](int32_t key) { return key < pred.lo; });
     if (s >= e) return RUN_NONE;

@@ -33,8 +33,9 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
-    mdb_value_filter as ValueFilter,
+    mdb_hist_request as HistRequest, mdb_value_filter as ValueFilter,
 };
+pub use sys::MDB_HIST_MAX_EDGES;
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
 pub use sys::{MDB_AGG_AVG, MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM};
@@ -340,6 +341,40 @@ fn check_bucket_cells(request: &BucketRequest, n_states: usize) -> Result<()> {
     Ok(())
 }
 
+/// The cells of a histogram call: `counts` is row-major `[n_groups][edges + 1]`.
+fn check_hist_cells(n_groups: u32, edges: &[f32], n_counts: usize) -> Result<()> {
+    if (n_groups as u64) * (edges.len() as u64 + 1) != n_counts as u64 {
+        return Err(HipError(format!(
+            "counts holds {} cells, the request n_groups * (edges + 1) = {} * {}",
+            n_counts, n_groups, edges.len() + 1
+        )));
+    }
+    Ok(())
+}
+
+fn hist_request(edges: &[f32], n_groups: u32, time_range: Option<(i64, i64)>) -> HistRequest {
+    let (t_lo, t_hi) = time_range.unwrap_or((i64::MIN, i64::MAX));
+    // (more edges than a u32 holds are more than MDB_HIST_MAX_EDGES: the library says so)
+    HistRequest { t_lo, t_hi, n_edges: u32::try_from(edges.len()).unwrap_or(u32::MAX), n_groups, flags: 0, reserved: 0 }
+}
+
+/// The cell of `value` under `edges`: the number of edges at or below it in totalOrder (host arithmetic, no GPU).
+/// Fails for edges `Context::hist` would reject.
+pub fn hist_cell_of(edges: &[f32], value: f32) -> Result<u32> {
+    let mut cell = 0u32;
+    let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+    check(unsafe { sys::mdb_hist_cell_of(edges.as_ptr(), n_edges, value, &mut cell) })?;
+    Ok(cell)
+}
+
+/// `(rank_lo, rank_hi, fraction)` of quantile `q` over `n_points` points: p = q * (n_points - 1), its floor, its ceil
+/// and p - floor(p) (host arithmetic, no GPU). `percentile_cont` is `lo + (hi - lo) * fraction`.
+pub fn quantile_positions(q: f64, n_points: u64) -> Result<(u64, u64, f64)> {
+    let (mut rank_lo, mut rank_hi, mut fraction) = (0u64, 0u64, 0f64);
+    check(unsafe { sys::mdb_quantile_positions(q, n_points, &mut rank_lo, &mut rank_hi, &mut fraction) })?;
+    Ok((rank_lo, rank_hi, fraction))
+}
+
 /// Group ids of a bucket call: one per segment row, if given.
 fn check_group_ids(segments: &SegmentsView, group_of_segment: Option<&[u32]>) -> Result<()> {
     if let Some(groups) = group_of_segment {
@@ -601,6 +636,84 @@ impl Context {
             sys::mdb_agg_buckets_filter_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                              request, filter, states.as_mut_ptr())
         })
+    }
+
+    /// A histogram of the values of `segments` inside `time_range`, without materialising a data point: replaces
+    /// GridExec -> AggregateExec for a distribution. `counts` is row-major `[n_groups][edges.len() + 1]` and the
+    /// points are ADDED to it; a value falls in the cell numbered by the edges at or below it in totalOrder.
+    /// `group_of_segment`: one id per segment row (`None`: all in group 0).
+    pub fn hist(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        n_groups: u32,
+        edges: &[f32],
+        time_range: Option<(i64, i64)>,
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_hist_cells(n_groups, edges, counts.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let request = hist_request(edges, n_groups, time_range);
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe {
+            sys::mdb_hist_batch(self.raw(), &segments.raw, groups, &request, edges.as_ptr(), counts.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::hist`] for several batches at once (rows in the order of the slice), counted as one batch.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn hist_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        n_groups: u32,
+        edges: &[f32],
+        time_range: Option<(i64, i64)>,
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_hist_cells(n_groups, edges, counts.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let request = hist_request(edges, n_groups, time_range);
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_hist_batch_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                     &request, edges.as_ptr(), counts.as_mut_ptr())
+        })
+    }
+
+    /// Exact order statistics of the values of `segments` inside `time_range`, in totalOrder: for every `q` in
+    /// [0, 1] the points of rank floor and ceil of `q * (n - 1)`, and `n`, the number of points (`None` when there is
+    /// none). What DataFusion's `median` / `percentile_cont` compute from the rebuilt points is
+    /// `lo + (hi - lo) * fraction` with [`quantile_positions`]; `approx_percentile_cont` approximates the same. At
+    /// most 16 quantiles per call.
+    pub fn quantile(
+        &self,
+        segments: &SegmentsView,
+        time_range: Option<(i64, i64)>,
+        q: &[f64],
+    ) -> Result<Option<(Vec<(f32, f32)>, u64)>> {
+        let (t_lo, t_hi) = time_range.unwrap_or((i64::MIN, i64::MAX));
+        let (mut lo, mut hi) = (vec![0f32; q.len()], vec![0f32; q.len()]);
+        let mut n_points = 0u64;
+        let n_q = u32::try_from(q.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_quantile_batch(self.raw(), &segments.raw, t_lo, t_hi, q.as_ptr(), n_q, lo.as_mut_ptr(),
+                                    hi.as_mut_ptr(), &mut n_points)
+        })?;
+        if n_points == 0 {
+            return Ok(None);
+        }
+        Ok(Some((lo.into_iter().zip(hi).collect(), n_points)))
     }
 
     /// Replaces the body of `try_compress_univariate_time_series` after its two argument checks

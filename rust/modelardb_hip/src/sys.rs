@@ -211,6 +211,28 @@ pub struct mdb_value_filter {
     pub reserved: u32,
 }
 
+/// Most edges of one histogram: 4 096 cells, 16 KB of keys in LDS, three passes cover the 32-bit keys.
+pub const MDB_HIST_MAX_EDGES: u32 = 4095;
+
+/// A value histogram for `mdb_hist_batch*`: `n_edges` edges (strictly increasing in the totalOrder of
+/// `mdb_value_filter`) cut the values into `n_edges + 1` cells; a point falls in the cell numbered by the edges at or
+/// below it.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct mdb_hist_request {
+    /// Inclusive time range (`i64::MIN` / `i64::MAX`: none).
+    pub t_lo: i64,
+    pub t_hi: i64,
+    /// 1 ..= `MDB_HIST_MAX_EDGES`.
+    pub n_edges: u32,
+    /// >= 1.
+    pub n_groups: u32,
+    /// Must be 0.
+    pub flags: u32,
+    /// Must be 0.
+    pub reserved: u32,
+}
+
 #[link(name = "mdb_hip")]
 unsafe extern "C" {
     // ---- lifetime ----------------------------------------------------------------------------
@@ -334,6 +356,21 @@ unsafe extern "C" {
     pub fn mdb_grid_batch_where_owned(ctx: *mut mdb_ctx, pred_fields: *const *const mdb_segments,
                                       filters: *const mdb_value_filter, n_preds: u32, target: *const mdb_segments,
                                       flags: u32, reserve_front: u64, out: *mut *mut mdb_grid_result) -> c_int;
+    // ---- value histograms and exact quantiles on segments (include/mdb.h) ----
+    pub fn mdb_hist_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                          request: *const mdb_hist_request, edges: *const f32, counts: *mut u64) -> c_int;
+    pub fn mdb_hist_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                              request: *const mdb_hist_request, edges: *const f32, counts: *mut u64) -> c_int;
+    pub fn mdb_hist_batch_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                               group_of_segment: *const *const u32, n_inputs: u32, request: *const mdb_hist_request,
+                               edges: *const f32, counts: *mut u64) -> c_int;
+    pub fn mdb_quantile_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
+                              n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
+    pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
+                                  n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
+    pub fn mdb_hist_cell_of(edges: *const f32, n_edges: u32, value: f32, cell: *mut u32) -> c_int;
+    pub fn mdb_quantile_positions(q: f64, n_points: u64, rank_lo: *mut u64, rank_hi: *mut u64,
+                                  fraction: *mut f64) -> c_int;
 
     // ---- fit (replaces try_compress_univariate_time_series, compression.rs:191-275) -----------------
     pub fn mdb_compress_series(ctx: *mut mdb_ctx, ts: *const i64, values: *const f32, n: u64,
@@ -439,3 +476,9 @@ const _: () = assert!(offset_of!(mdb_value_filter, v_lo) == 16);
 const _: () = assert!(offset_of!(mdb_value_filter, v_hi) == 20);
 const _: () = assert!(offset_of!(mdb_value_filter, flags) == 24);
 const _: () = assert!(offset_of!(mdb_value_filter, reserved) == 28);
+const _: () = assert!(size_of::<mdb_hist_request>() == 32);
+const _: () = assert!(offset_of!(mdb_hist_request, t_hi) == 8);
+const _: () = assert!(offset_of!(mdb_hist_request, n_edges) == 16);
+const _: () = assert!(offset_of!(mdb_hist_request, n_groups) == 20);
+const _: () = assert!(offset_of!(mdb_hist_request, flags) == 24);
+const _: () = assert!(offset_of!(mdb_hist_request, reserved) == 28);
