@@ -300,11 +300,11 @@ __device__ __forceinline__ void agg_range_body(DevSegments s, int64_t t_lo, int6
         if (mode == AGG_SUM_ONLY_DEFERRED && s.model_type_id[i] != MDB_MACAQUE_V_ID) continue;
         SegInfo info = analyse_segment(s, i, walked_totals);
         uint32_t error = info.error;
-        // MacaqueV segments with cursors into their stream: piece by piece (k_agg_mv_range, mdb_grid.hip).
+        // MacaqueV segments with cursors into their stream: piece by piece (k_agg_mv_range, mdb_agg_mv.hip).
         const bool has_pieces = indexed_piece_base && indexed_piece_base[i + 1] > indexed_piece_base[i];
         if (has_pieces && mv_range_by_pieces(s, i, info)) continue;
         const bool tail_by_pieces = has_pieces && mv_range_tail_by_pieces(s, i, info);
-        // Long MacaqueV streams are left to the decoders of mdb_grid.hip (see AGG_SUM_DEFER).
+        // Long MacaqueV streams are left to the decoders of mdb_agg_mv.hip (see AGG_SUM_DEFER).
         const uint32_t deferred_values =
             (mode != AGG_SUM_ALL && !error && s.model_type_id[i] == MDB_MACAQUE_V_ID)
                 ? mv_deferred_values(s, i, info, mv_min_values, range) : 0u;
@@ -466,7 +466,7 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
     const TsWalkRange *walked_ranges = nullptr;
     const unsigned int *walked_error = nullptr; // (what the walk found wrong with a stream)
     // A batch that stays on the device has (from its first grid or aggregate call on) cursors into its MacaqueV
-    // streams: SUM then decodes them piece by piece (mdb_grid.hip, k_agg_mv_pieces) instead of one lane per stream.
+    // streams: SUM then decodes them piece by piece (mdb_agg_mv.hip, k_agg_mv_pieces) instead of one lane per stream.
     if (sums_wanted && mv_index_ensure(ctx, in)) return 1;
     // Under a time range the same cursors let the points inside it be decoded piece by piece (MDB_AGG_RANGE_PIECES=0:
     // one lane per stream, or the parallel decoder for the long ones).
@@ -603,7 +603,7 @@ int agg_run(mdb_ctx *ctx, const mdb_segments *in, bool range, int64_t t_lo, int6
         if (walked_sums || !walked_totals) resident->agg_walk_with_sums = true;
     }
     if (host.deferred > 0) {
-        // Long MacaqueV streams were left aside for the decoders of mdb_grid.hip ...
+        // Long MacaqueV streams were left aside for the decoders of mdb_agg_mv.hip ...
         bool handled = false;
         DeferredTotals totals;
         const TimeRange time_range = {t_lo, t_hi, range ? 1 : 0};

@@ -1,7 +1,7 @@
 // mdb_agg_dev.hpp - the points of one segment inside a time range, aggregated without materialising them
 // (segment_range: ONE walk of a segment's model and streams, with a selector that says which points count - every one,
 // by value, or by row): shared by the time-range, filtered and masked aggregates (mdb_agg.hip: k_agg_range,
-// k_agg_filter, k_agg_mask) and the bucketed ones (mdb_buckets.hip, and their MacaqueV pieces in mdb_grid.hip).
+// k_agg_filter, k_agg_mask) and the bucketed ones (mdb_buckets.hip).
 #pragma once
 
 #include "mdb_filter.hpp"
@@ -22,7 +22,14 @@ struct RangeAcc {
         min = min_num(min, v);
         max = max_num(max, v);
     }
+    __device__ __forceinline__ void merge(const RangeAcc &other) {
+        sum += other.sum;
+        count += other.count;
+        min = min_num(min, other.min);
+        max = max_num(max, other.max);
+    }
 };
+static_assert(sizeof(RangeAcc) == 24, "arrays of partials are laid out in scratch by this size");
 
 __device__ __forceinline__ float model_value_at(const SegDesc &d, uint32_t type, int64_t t) {
     return type == MDB_PMC_MEAN_ID ? d.value : (float)(d.slope * (double)t + d.intercept);
@@ -195,7 +202,7 @@ __device__ __forceinline__ void segment_range(const DevSegments &s, uint64_t i, 
     }
 }
 
-// ---- date_bin buckets (mdb_buckets.hip; their MacaqueV pieces in mdb_grid.hip) ------------------------------
+// ---- date_bin buckets (mdb_buckets.hip) ---------------------------------------------------------------------
 
 struct BucketPartial { // one pair's points, or a run's: the layout of mdb_agg_state
     double sum;
@@ -268,8 +275,8 @@ __device__ __forceinline__ int64_t buckets_last_time(const BucketRequest &r) {
 }
 
 // Is segment i's MacaqueV stream - its values (MacaqueV, regular timestamps, no residuals) or the residual tail of a
-// PMC-Mean / Swing segment with regular timestamps - aggregated per bucket piece by piece (k_agg_bucket_pieces,
-// mdb_grid.hip) from the batch's cursor index (piece_base)? The same test as the range path's (mv_range_by_pieces /
+// PMC-Mean / Swing segment with regular timestamps - aggregated per bucket piece by piece (k_agg_bucket_pieces)
+// from the batch's cursor index (piece_base)? The same test as the range path's (mv_range_by_pieces /
 // mv_range_tail_by_pieces), evaluated identically by k_agg_bucket_partials, which then leaves those points out.
 __device__ __forceinline__ bool bucket_values_by_pieces(const DevSegments &s, uint64_t i, const SegInfo &info,
                                                         const unsigned long long *piece_base) {
@@ -279,16 +286,6 @@ __device__ __forceinline__ bool bucket_tail_by_pieces(const DevSegments &s, uint
                                                       const unsigned long long *piece_base) {
     return piece_base && piece_base[i + 1] > piece_base[i] && mv_range_tail_by_pieces(s, i, info);
 }
-
-// mdb_grid.hip: the entries of the MacaqueV pieces taken above. bucket_pieces_count sizes them (offsets: per piece of
-// the index, n_pieces + 1, in scratch); bucket_pieces_entries writes the entries [e0, e1) to keys / out (at e - e0),
-// with the values that pass `filter` only (nullptr: every value; the entries are the same either way).
-int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
-                        const MvIndex &index, const unsigned long long **offsets, unsigned long long *total);
-int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
-                          const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
-                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
-                          const ValueKeys *filter);
 
 // mdb_buckets.hip: the group ids of host batches (groups[k]: rows[k] ids or nullptr, groups itself may be nullptr) as
 // one device array in the context's scratch (*out nullptr: every segment in group 0).

@@ -15,7 +15,7 @@
 //                          per pair (segment_range's closed forms, its tail decode for residuals). MacaqueV values or
 //                          irregular timestamps: the stream is decoded once, a partial flushed at each bucket edge -
 //                          unless the stream is in the batch's cursor index (regular timestamps: MacaqueV values, the
-//                          residual tails of PMC-Mean / Swing): then k_agg_bucket_pieces (mdb_grid.hip) decodes it one
+//                          residual tails of PMC-Mean / Swing): then k_agg_bucket_pieces decodes it one
 //                          lane per piece of 64 values and writes one entry {key, partial} per bucket a piece reaches;
 //                          the entries are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check     are the keys non-decreasing in pair order (ModelarDB's storage order: segments by tags, then
@@ -27,6 +27,7 @@
 //                          atomics, the order of every addition fixed by the pair order: run-to-run deterministic.
 // Bytes (Swing on regular timestamps): ~70 B of metadata per segment read, 32 B per pair written and read back.
 #include "mdb_agg_dev.hpp"
+#include "mdb_mv_pieces.hpp"
 #include "mdb_scan.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -281,6 +282,171 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_fold(BucketTree t
     if ((which_mask & MDB_AGG_MAX) && !(acc.max != acc.max) && (cell.max != cell.max || acc.max > cell.max))
         cell.max = acc.max;
     cells[key] = cell;
+}
+
+// ---- the pieces of MacaqueV streams ----------------------------------------------------------------------------
+// The streams bucket_values_by_pieces / bucket_tail_by_pieces take (regular timestamps: point k at start + k delta)
+// are aggregated like k_agg_mv_range does under a time range - one lane per piece of 64 values, every lane decoding
+// in every step - but each lane flushes a partial at every bucket edge: ENTRIES {key, partial}, one per bucket its
+// visible values reach (empty ones included), at offsets a count per piece and a scan have given. Entries of one
+// stream follow each other in key order; buckets_run reduces and folds them like its (segment, bucket) pairs.
+
+// The visible values [from, upto) of the piece (segment-level indices) and the buckets [b_first, b_last] they reach;
+// false: the piece is not taken or holds no visible value.
+__device__ __forceinline__ bool bucket_piece_span(const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
+                                                  const PieceCursor &cursor, SegInfo *info_out, uint32_t *from,
+                                                  uint32_t *upto, uint64_t *b_first, uint64_t *b_last) {
+    const uint32_t i = cursor.segment(), point_index = cursor.point_index(), n_values = cursor.n_values();
+    const uint4 ts_view = s.timestamps.views[i];
+    if ((int32_t)ts_view.x > 0 && (view_inline_byte(ts_view, 0) & 0x80u) != 0) return false; // (irregular: not taken)
+    uint64_t unused = 0;
+    if (bucket_span(s.start_time[i], s.end_time[i], r, &unused) == 0) return false;
+    const SegInfo info = analyse_segment(s, i);
+    if (!(cursor.residual() ? bucket_tail_by_pieces(s, i, info, piece_base) : bucket_values_by_pieces(s, i, info, piece_base)))
+        return false;
+    const int64_t lo = r.t_lo > r.origin ? r.t_lo : r.origin;
+    const int64_t last = buckets_last_time(r);
+    const int64_t hi = r.t_hi < last ? r.t_hi : last;
+    uint32_t k_lo = 0, k_hi = 0;
+    if (lo > hi || !regular_index_interval(info.desc.start, info.desc.delta, info.desc.n_total, lo, hi, &k_lo, &k_hi))
+        return false;
+    *from = max(k_lo, point_index);
+    *upto = min(k_hi + 1, point_index + n_values);
+    if (*from >= *upto) return false;
+    const SegDesc &d = info.desc;
+    const uint64_t width = (uint64_t)r.width;
+    *b_first = ((uint64_t)(d.start + (int64_t)((uint64_t)*from * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
+    *b_last = ((uint64_t)(d.start + (int64_t)((uint64_t)(*upto - 1) * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
+    *info_out = info;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_agg_bucket_piece_count(DevSegments s, BucketRequest r,
+                                                                 const unsigned long long *__restrict__ piece_base,
+                                                                 const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
+                                                                 unsigned long long *__restrict__ counts) {
+    const unsigned long long piece = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (piece >= n_pieces) return;
+    SegInfo info;
+    uint32_t from, upto;
+    uint64_t b_first, b_last;
+    counts[piece] = bucket_piece_span(s, r, piece_base, load_piece_cursor(cursors, piece), &info, &from, &upto, &b_first, &b_last)
+                        ? b_last - b_first + 1 : 0;
+}
+
+// Writes the entries [e0, e1) of the call (entry e at e - e0). Pred (AllValues, or the ValueKeys of
+// mdb_agg_buckets_filter*) says which decoded values are accumulated: the entries, and the decode, stay the same.
+template <typename Pred>
+__global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, BucketRequest r, const uint32_t *__restrict__ groups,
+                                                                const unsigned long long *__restrict__ piece_base,
+                                                                const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
+                                                                const unsigned long long *__restrict__ offsets,
+                                                                unsigned long long e0, unsigned long long e1,
+                                                                unsigned long long *__restrict__ keys,
+                                                                BucketPartial *__restrict__ out, Pred pred) {
+    static_assert(!Pred::by_row, "the buckets select by value: rows are not threaded through them");
+    __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
+    const int lane = threadIdx.x;
+    const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
+    const uint8_t *values_first = first_buffer(s.values), *residuals_first = first_buffer(s.residuals); // (see view_data())
+    uint32_t to_decode = 0, to_skip = 0, point_index = 0;
+    uint64_t b_first = 0, b_last = 0, base = 0, row = 0;
+    int64_t start = 0, delta = 0;
+    PieceReader reader;
+    PieceState state = piece_state_idle();
+    reader.idle(cursors);
+    if (piece < n_pieces && offsets[piece + 1] > e0 && offsets[piece] < e1) {
+        const PieceCursor cursor = load_piece_cursor(cursors, piece);
+        SegInfo info;
+        uint32_t from, upto;
+        if (bucket_piece_span(s, r, piece_base, cursor, &info, &from, &upto, &b_first, &b_last)) {
+            point_index = cursor.point_index();
+            // (a tail is XOR-seeded with the model's last RECONSTRUCTED value, models/mod.rs:241-249: what grid() sees)
+            const uint32_t seed = cursor.residual() ? __float_as_uint(info.desc.value) : 0u;
+            to_decode = upto - point_index;
+            to_skip = from - point_index;
+            start = info.desc.start;
+            delta = info.desc.delta;
+            base = offsets[piece];
+            row = (uint64_t)(groups ? groups[cursor.segment()] : 0u) * r.n_buckets;
+            piece_open(reader, s, cursor, values_first, residuals_first);
+            state = piece_state(cursor, seed);
+        }
+    }
+    if (!__any(to_decode > 0)) return;
+    RangeAcc acc;
+    uint64_t bucket = b_first;
+    auto flush = [&]() {
+        const uint64_t e = base + (bucket - b_first);
+        if (e >= e0 && e < e1) {
+            keys[e - e0] = row + bucket;
+            out[e - e0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
+        }
+        acc = RangeAcc();
+        bucket++;
+    };
+    auto take = [&](uint32_t k, uint32_t bits) {
+        if (k < to_skip || k >= to_decode) return;
+        const int64_t t = start + (int64_t)((uint64_t)(point_index + k) * (uint64_t)delta);
+        const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
+        while (bucket < b) flush();
+        if (pred.counts(__uint_as_float(bits), 0)) acc.point(__uint_as_float(bits)); // (by value: Pred::by_row is false)
+    };
+    piece_start(reader, ring, lane);
+    for (uint32_t k = 0, most = wave_max_u32(to_decode); k < most; k += 2) {
+        if (__any(reader.hungry())) reader.top_up(ring, lane);
+        const uint32_t even = piece_decode_value(reader, state, ring, lane);
+        const uint32_t odd = piece_decode_value(reader, state, ring, lane);
+        take(k, even);
+        take(k + 1, odd);
+    }
+    if (to_decode > 0) flush(); // (bucket == b_last)
+}
+
+// The entries of the pieces taken above. bucket_pieces_count sizes them (offsets: per piece of the index, n_pieces + 1,
+// in scratch); bucket_pieces_entries writes the entries [e0, e1) to keys / out (at e - e0), with the values that pass
+// `filter` only (nullptr: every value; the entries are the same either way).
+static int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
+                               const MvIndex &index, const unsigned long long **offsets_out, unsigned long long *total) {
+    *total = 0;
+    const uint64_t n = index.n_pieces;
+    void *p = nullptr;
+    const uint64_t counts_bytes = align_up(n * 8, 256), offsets_bytes = align_up((n + 1) * 8, 256);
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_PIECES, counts_bytes + offsets_bytes + scan_block_sums_bytes(n) + 256, &p))
+        return 1;
+    unsigned long long *counts = static_cast<unsigned long long *>(p);
+    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes);
+    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes + offsets_bytes);
+    {
+        LaunchTimer timer(ctx, "k_agg_bucket_piece_count");
+        hipLaunchKernelGGL(k_agg_bucket_piece_count, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, s, r,
+                           piece_base, static_cast<const MvCursor *>(index.cursors), (unsigned long long)n, counts);
+    }
+    if (device_exclusive_scan(ctx, ItemsOf<unsigned long long>{counts}, n, offsets, block_sums, "k_agg_bucket_piece_count")) return 1;
+    MDB_HIP_CHECK(hipMemcpyAsync(total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    *offsets_out = offsets;
+    return 0;
+}
+
+static int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
+                                 const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
+                                 unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
+                                 const ValueKeys *filter) {
+    const uint64_t n = index.n_pieces;
+    const dim3 blocks((uint32_t)((n + MDB_WAVE - 1) / MDB_WAVE));
+    const MvCursor *cursors = static_cast<const MvCursor *>(index.cursors);
+    if (filter) {
+        LaunchTimer timer(ctx, "k_agg_bucket_pieces_filter");
+        hipLaunchKernelGGL(k_agg_bucket_pieces<ValueKeys>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
+                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, *filter);
+    } else {
+        LaunchTimer timer(ctx, "k_agg_bucket_pieces");
+        hipLaunchKernelGGL(k_agg_bucket_pieces<AllValues>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
+                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, AllValues());
+    }
+    return 0;
 }
 
 static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + BUCKET_THREADS - 1) / BUCKET_THREADS); }

@@ -88,7 +88,7 @@ enum ScratchSlot {
     SCRATCH_BUCKET_TREE,  // ... the upper levels of the reduction
     SCRATCH_BUCKET_CELLS, // ... the working copy of the caller's cells (host forms, several slices)
     SCRATCH_BUCKET_GROUPS, // ... the group ids of the host forms
-    SCRATCH_BUCKET_PIECES, // ... entry counts and offsets of the MacaqueV pieces (mdb_grid.hip)
+    SCRATCH_BUCKET_PIECES, // ... entry counts and offsets of the MacaqueV pieces (bucket_pieces_count)
     SCRATCH_FILTER_SEGMENTS, // mdb_grid_*_filter*: per segment its interval, row count, offsets and the scans
     SCRATCH_FILTER_GATHER,   // ... the columns of the segments whose points are tested one by one
     SCRATCH_FILTER_SLICE,    // ... one slice of their rebuilt points
@@ -353,7 +353,7 @@ struct DevSegments {
     DevCol residuals;
 };
 
-// mdb_grid.hip, for mdb_agg.hip: the MacaqueV decoders as a service to the aggregates (see there).
+// mdb_grid.hip and mdb_agg_mv.hip, for mdb_agg.hip: the MacaqueV decoders as a service to the aggregates (see there).
 struct DeferredTotals {
     double sum = 0.0;
     long long count = 0;
@@ -364,6 +364,7 @@ uint32_t macaque_parallel_min_values(bool *forced);
 struct DevSegments;
 // (with a cursor index into the batch's MacaqueV streams, MvIndex: their f32 sums, 2 per segment)
 int mv_index_ensure(mdb_ctx *ctx, const mdb_segments *in);
+std::shared_ptr<MvIndex> mv_index_lookup(const mdb_segments *in);
 int mv_index_for_range(mdb_ctx *ctx, const mdb_segments *in, std::shared_ptr<MvIndex> *index, const unsigned long long **piece_base);
 int mv_index_stream_sums(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const uint32_t *known_totals,
                          const float **stream_sums, const unsigned long long **only_with_pieces);

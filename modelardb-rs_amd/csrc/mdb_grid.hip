@@ -26,10 +26,13 @@
 //                    value streams, residual tails (<= 255 values) and the few irregular timestamp
 //                    streams short enough to live inside their view overwrite the placeholders.
 // Algorithmic bytes: 73 B/segment read + 12 B/point written (8 B timestamp + 4 B value).
+// The MacaqueV decoders: mdb_mv_pieces.hpp (a lane per piece or per stream), mdb_mv_parallel.hip (many lanes per
+// stream); the cursor index is built here (mv_index_*), the aggregates that read it are mdb_agg_mv.hip.
 #include "mdb_agg_dev.hpp"
 #include "mdb_segment_dev.hpp"
 #include "mdb_scan.hpp"
 #include "mdb_macaque_parallel.hpp"
+#include "mdb_mv_pieces.hpp"
 
 #include <atomic>
 #include <cfloat>
@@ -1053,165 +1056,6 @@ struct TsPieceCount { // pieces of the stream of segment i, 0 if it has no check
     }
 };
 
-// ---- the serial kernel -------------------------------------------------------------------------------
-//
-// One lane per segment that carries a serial dependency, one wave per workgroup. MacaqueV streams
-// (a model's values and/or the residual tail) are decoded from an LDS ring: every lane keeps the
-// next SERIAL_RING_WORDS 32-bit words of ITS bitstream in LDS ([slot][lane], bank-conflict free),
-// and when any lane runs low the whole wave tops all rings up with independent predicated loads
-// issued back to back - one memory latency per ~24 words instead of one per word. The decode itself
-// stays sequential per stream: value i's position depends on every earlier value.
-// Irregular (delta-of-delta) timestamps are rare and keep the direct reader.
-
-constexpr int SERIAL_RING_WORDS = 32;
-constexpr int SERIAL_TOPUP_WORDS = 24;
-constexpr int SERIAL_THREADS = MDB_WAVE;
-
-struct RingBitReader {
-    const uint32_t *words; // aligned base in global memory
-    uint32_t n_words;
-    uint32_t next_word; // next word to move from the ring into the bit buffer
-    uint32_t loaded;    // words [next_word, loaded) are in the ring
-    uint64_t buffer;    // MSB aligned
-    int32_t available;
-    uint32_t skip_bits; // slack bits in front of the first payload byte
-    uint64_t used_bits;
-    uint64_t total_bits;
-    uint32_t ahead;     // refill(): ring word next_word, byte swapped
-
-    __device__ __forceinline__ void begin(const uint8_t *bytes, uint64_t nbytes) {
-        uintptr_t address = reinterpret_cast<uintptr_t>(bytes);
-        uint32_t misalign = (uint32_t)(address & 3u);
-        words = reinterpret_cast<const uint32_t *>(address - misalign);
-        n_words = (uint32_t)((nbytes + misalign + 3u) >> 2);
-        next_word = 0;
-        loaded = 0;
-        buffer = 0;
-        available = 0;
-        skip_bits = 8u * misalign;
-        used_bits = 0;
-        total_bits = nbytes * 8u;
-        ahead = 0;
-    }
-    __device__ __forceinline__ bool hungry() const { return loaded < n_words && loaded - next_word < 3; }
-    __device__ __forceinline__ void pull(const uint32_t (*ring)[MDB_WAVE], int lane) {
-        while (available <= 32 && next_word < loaded) {
-            uint32_t w = __builtin_bswap32(ring[next_word % SERIAL_RING_WORDS][lane]);
-            next_word += 1;
-            if (skip_bits) { // only the very first word can carry slack bytes
-                buffer |= ((uint64_t)w << 32) << skip_bits;
-                available += 32 - (int32_t)skip_bits;
-                skip_bits = 0;
-            } else {
-                buffer |= (uint64_t)w << (32 - available);
-                available += 32;
-            }
-        }
-    }
-    __device__ __forceinline__ uint32_t get(uint32_t count, const uint32_t (*ring)[MDB_WAVE], int lane) {
-        if (count == 0) return 0;
-        pull(ring, lane);
-        uint32_t value = (uint32_t)(buffer >> (64u - count));
-        buffer <<= count;
-        available -= (int32_t)count;
-        used_bits += count;
-        return value;
-    }
-    // The same without branches (64 lanes that each stand somewhere else in a code execute both sides
-    // of every branch anyway): at most one word, so a caller that needs up to 45 bits refills before
-    // the control bits and again before the payload. Needs 0 <= available while words remain, which
-    // holds from the second refill of a stream on (the first word may bring as few as 8 bits).
-    // The word comes out of a register (`ahead` = ring word next_word, see look_ahead) so that no LDS
-    // latency sits on the chain from one code to the next.
-    __device__ __forceinline__ void refill(const uint32_t (*ring)[MDB_WAVE], int lane) {
-        const bool want = available <= 32 && next_word < loaded;
-        const uint64_t placed = (((uint64_t)ahead << 32) << skip_bits) >> (available & 63);
-        buffer |= want ? placed : 0ull;
-        available += want ? 32 - (int32_t)skip_bits : 0;
-        skip_bits = want ? 0u : skip_bits;
-        next_word += want ? 1u : 0u;
-        look_ahead(ring, lane);
-    }
-    // Ring slot of next_word, read whether or not it has been filled yet: it is not used before it has
-    // (refill() tests next_word < loaded), and a stream that starts calls this again after its first
-    // top-up. A top-up never overwrites the slots [next_word, loaded).
-    __device__ __forceinline__ void look_ahead(const uint32_t (*ring)[MDB_WAVE], int lane) {
-        ahead = __builtin_bswap32(ring[next_word % SERIAL_RING_WORDS][lane]);
-    }
-    __device__ __forceinline__ void consume(uint32_t count) {
-        buffer <<= count;
-        available -= (int32_t)count;
-        used_bits += count;
-    }
-    __device__ __forceinline__ bool overrun() const { return used_bits > total_bits; }
-};
-
-struct MacaqueStream {
-    uint32_t remaining;  // values still to decode
-    uint32_t position;   // index of the next value inside the whole segment
-    uint32_t last;       // bits of the previous value
-    uint32_t leading, trailing;
-    bool first_is_raw;   // the next value is stored as 32 raw bits (macaque_v.rs:289-293)
-    bool fresh;          // nothing has been read from the stream yet
-};
-
-// Tops the ring of every lane of the wave up at once (the caller has found a hungry lane): independent
-// predicated loads first, then the LDS writes.
-__device__ __forceinline__ void ring_top_up(RingBitReader &reader, uint32_t (*ring)[MDB_WAVE], int lane, bool active) {
-    uint32_t fetched[SERIAL_TOPUP_WORDS];
-    const uint32_t first = reader.loaded;
-    const uint32_t room = active ? SERIAL_RING_WORDS - (reader.loaded - reader.next_word) : 0u;
-#pragma unroll
-    for (int k = 0; k < SERIAL_TOPUP_WORDS; k++) {
-        const uint32_t index = first + k;
-        fetched[k] = ((uint32_t)k < room && index < reader.n_words) ? load_global(reader.words + index) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < SERIAL_TOPUP_WORDS; k++) {
-        const uint32_t index = first + k;
-        if ((uint32_t)k < room && index < reader.n_words) ring[index % SERIAL_RING_WORDS][lane] = fetched[k];
-    }
-    reader.loaded = min(reader.n_words, first + min(room, (uint32_t)SERIAL_TOPUP_WORDS));
-}
-
-// One value (macaque_v.rs:297-322): `10` it repeats, `0` + the bits of the previous window, `11` + 5
-// bits leading zeros + 6 bits length + the bits - at most 45 bits, of which the control bits come off
-// the top of the 64-bit buffer after one refill and the payload after another. Every lane of the wave
-// stands at a different kind of code, so the three cases are computed with selects rather than
-// branched to. Returns the bits of the value (stream.last is updated); *malformed: the window is
-// impossible, the value returned is the previous one and the caller stops.
-__device__ __forceinline__ uint32_t ring_decode_value(RingBitReader &reader, MacaqueStream &stream,
-                                                      const uint32_t (*ring)[MDB_WAVE], int lane, bool *malformed) {
-    if (stream.fresh) {
-        reader.look_ahead(ring, lane);
-        reader.refill(ring, lane);
-        stream.fresh = false;
-    }
-    reader.refill(ring, lane);
-    const uint32_t top = (uint32_t)(reader.buffer >> 51); // 13 bits: c0 c1 lz[5] len[6]
-    const bool raw = stream.first_is_raw;                 // 32 raw bits, no control bits
-    const bool c0 = (top >> 12) != 0u, c1 = ((top >> 11) & 1u) != 0u;
-    const bool opens = !raw && c0 && c1;
-    const bool repeats = !raw && c0 && !c1;
-    const uint32_t header_bits = raw ? 0u : (c0 ? (c1 ? 13u : 2u) : 1u);
-    const uint32_t leading = opens ? ((top >> 6) & 31u) : stream.leading;
-    const uint32_t trailing = opens ? 32u - (top & 63u) - leading : stream.trailing;
-    uint32_t meaningful = 32u - leading - trailing;
-    *malformed = !raw && !repeats && (meaningful > 32u || trailing > 31u);
-    const bool silent = repeats || *malformed; // no payload: the value is the previous one
-    stream.leading = leading;
-    stream.trailing = trailing;
-    stream.first_is_raw = false;
-    meaningful = raw ? 32u : (silent ? 0u : meaningful);
-    reader.consume(header_bits);
-    reader.refill(ring, lane);
-    const uint32_t payload = (uint32_t)((reader.buffer >> 1) >> (63u - meaningful)); // 0 bits: 0
-    reader.consume(meaningful);
-    const uint32_t bits = raw ? payload : (stream.last ^ (payload << (trailing & 31u)));
-    stream.last = bits;
-    return bits;
-}
-
 // ---- random access into MacaqueV streams: the cursor index of a resident batch -----------------------------
 //
 // macaque_v.rs:272-323 decodes a stream from its first bit: where code i begins depends on every code before it,
@@ -1232,19 +1076,8 @@ __device__ __forceinline__ uint32_t ring_decode_value(RingBitReader &reader, Mac
 // grid() seeds such a segment's residual tail with (the reference's compressor never makes one, a foreign batch
 // may), and the walk leaves it in the tail's cursors (chain_seed).
 
-// (MvCursor, MV_PIECE_VALUES, MV_WINDOW_*: mdb_common.hpp)
-
-// Values of the two streams of segment i: the model's (MacaqueV segments only) and the residual tail's.
-__device__ __forceinline__ void mv_stream_lengths(const DevSegments &s, uint64_t i, const uint32_t *known_totals,
-                                                  uint32_t *n_model_values, uint32_t *n_residuals, uint32_t *n_model_points,
-                                                  uint32_t *error) {
-    const SegInfo info = analyse_segment(s, i, known_totals, nullptr, false);
-    *error = info.error;
-    const uint32_t n_res = info.desc.n_total - info.desc.n_model;
-    *n_model_points = info.desc.n_model;
-    *n_model_values = (info.desc.flags & FLAG_TYPE_MASK) == MDB_MACAQUE_V_ID ? info.desc.n_model : 0u;
-    *n_residuals = n_res;
-}
+// (MvCursor, MV_PIECE_VALUES, MV_WINDOW_*: mdb_host_side.hpp; mv_stream_lengths, the decoder of a piece and the ring
+// of the serial kernels (RingBitReader, ring_decode_value; SERIAL_THREADS lanes, one wave per workgroup): mdb_mv_pieces.hpp)
 
 struct MvIndexPieces { // pieces of segment i (0 for a malformed one: the batch is then not indexed at all)
     DevSegments s;
@@ -1348,142 +1181,6 @@ __global__ __launch_bounds__(SERIAL_THREADS) void k_mv_index_walk(DevSegments s,
     if (walked) atomicAdd(verdict + 1, walked);
 }
 
-// ---- the same step for the kernels that decode one PIECE per lane, on 32-bit words -------------------------------
-//
-// ring_decode_value's step over a 64-bit buffer with a reader of its own per lane cost the wave 104 vector instructions
-// per value (every shift, add and compare on 64 bits is two or three instructions, two refills per code each rotated
-// four words through registers, the bit position was 64 bits wide). Here a lane keeps the three big-endian words its next code can reach into (a code is at most 45 bits:
-// 13 of header, 32 of payload) and the bit offset into the first; header and payload come out of them with one funnel
-// shift each, and the words behind them come from a ring of the lane's stream in LDS ([word][lane]: the lanes of a
-// wave read different rows of their own column, two lanes per bank at worst), read at the top of the step and needed
-// at its end. The ring is topped up for the whole wave from 16-byte chunks that were loaded one top-up earlier.
-constexpr int PIECE_RING_WORDS = 16;
-constexpr int PIECE_RING_ROWS = PIECE_RING_WORDS + 4; // (and four rows nobody reads: where a lane without room puts its chunk)
-struct PieceReader {
-    const uint4 *chunks; // 16-byte aligned; chunk k holds words [4 k, 4 k + 4) of the stream as this reader counts them
-    uint32_t last_chunk; // the last one that holds payload (loads never go behind it)
-    uint32_t loaded;     // words [.., loaded) have been put into the ring; a multiple of 4
-    uint32_t word;       // index of w0
-    uint32_t w0, w1, w2; // words word, word + 1, word + 2 (big endian: the stream's first bit on top)
-    uint32_t shift;      // bits of w0 already consumed (0..31)
-    uint4 ahead, further, beyond, last; // chunks loaded / 4 .. loaded / 4 + 3, on their way from memory
-
-    __device__ __forceinline__ uint4 load(uint32_t index) const { return load_global(chunks + min(index, last_chunk)); }
-    // nbytes > 0
-    __device__ __forceinline__ void open(const uint8_t *bytes, uint64_t nbytes, uint64_t start_bit) {
-        const uintptr_t address = reinterpret_cast<uintptr_t>(bytes);
-        const uint32_t misalign = (uint32_t)(address & 15u);
-        const uint64_t first_bit = 8ull * misalign + start_bit; // counted from the aligned base
-        const uint64_t skipped = first_bit >> 7;                // whole chunks in front of it
-        const uint64_t all_chunks = (nbytes + misalign + 15u) >> 4;
-        chunks = reinterpret_cast<const uint4 *>(address - misalign) + skipped;
-        last_chunk = (uint32_t)(all_chunks > skipped ? all_chunks - skipped - 1 : 0u);
-        word = (uint32_t)((first_bit >> 5) & 3u);
-        shift = (uint32_t)(first_bit & 31u);
-    }
-    // A lane without a piece runs through the same straight-line code as the others (nothing it makes is looked at):
-    // its reader reads `anywhere`, 16 bytes that may be read.
-    __device__ __forceinline__ void idle(const void *anywhere) {
-        chunks = reinterpret_cast<const uint4 *>(reinterpret_cast<uintptr_t>(anywhere) & ~(uintptr_t)15u);
-        last_chunk = 0;
-        word = shift = 0;
-    }
-    __device__ __forceinline__ void begin() { // (every lane, after open() or idle())
-        loaded = 0;
-        w0 = w1 = w2 = 0;
-        ahead = load(0);
-        further = load(1);
-        beyond = load(2);
-        last = load(3);
-    }
-    // Can the next TWO values be decoded without another look? (a value moves up at most two words; the second one's
-    // words behind w2 are rows word + 5 and word + 6 then)
-    __device__ __forceinline__ bool hungry() const { return loaded < word + 7u; }
-    // The whole wave, without a branch: every lane puts the chunk it has waited for into its column - behind what it
-    // has there, or into rows nobody reads when there is no room for it (a lane far ahead of the hungry one) - and
-    // asks for another one (the same one again when it could not place this one). Four chunks are under way: the one
-    // placed now was asked for four top-ups - the time of a dozen values - ago.
-    __device__ __forceinline__ void top_up(uint32_t (*ring)[MDB_WAVE], int lane) {
-        const bool room = loaded <= word + ((uint32_t)PIECE_RING_WORDS - 4u);
-        const uint32_t row = room ? loaded & (uint32_t)(PIECE_RING_WORDS - 1) : (uint32_t)PIECE_RING_WORDS;
-        ring[row + 0][lane] = ahead.x;
-        ring[row + 1][lane] = ahead.y;
-        ring[row + 2][lane] = ahead.z;
-        ring[row + 3][lane] = ahead.w;
-        loaded += room ? 4u : 0u;
-        auto move_up = [room](uint4 &to, const uint4 &from) {
-            to.x = room ? from.x : to.x;
-            to.y = room ? from.y : to.y;
-            to.z = room ? from.z : to.z;
-            to.w = room ? from.w : to.w;
-        };
-        move_up(ahead, further);
-        move_up(further, beyond);
-        move_up(beyond, last);
-        last = load((loaded >> 2) + 3u);
-    }
-    // After the first top-ups: the three words the first code can reach into.
-    __device__ __forceinline__ void start(const uint32_t (*ring)[MDB_WAVE], int lane) {
-        w0 = __builtin_bswap32(ring[word][lane]);
-        w1 = __builtin_bswap32(ring[word + 1u][lane]);
-        w2 = __builtin_bswap32(ring[word + 2u][lane]);
-    }
-};
-
-struct PieceState {
-    uint32_t last;        // bits of the previous value
-    uint32_t trailing;    // of the window the last `11` code opened
-    uint32_t window_bits; // 32 - leading - trailing of that window (0: none yet - the index has seen every code: there is)
-    bool raw;             // the next value is 32 raw bits (macaque_v.rs:289-293)
-};
-
-// The 32 bits that begin `shift` (0..31) bits into the 64 bits high:low.
-__device__ __forceinline__ uint32_t bits_at(uint32_t high, uint32_t low, uint32_t shift) {
-    return (uint32_t)(((((uint64_t)high) << 32) | low) << shift >> 32);
-}
-
-// One value (macaque_v.rs:297-322; the cursor index has seen every window of the stream: they are possible ones).
-__device__ __forceinline__ uint32_t piece_decode_value(PieceReader &reader, PieceState &state, const uint32_t (*ring)[MDB_WAVE], int lane) {
-    // (the two words that may move up, asked for now, needed last)
-    const uint32_t behind0 = ring[(reader.word + 3u) & (uint32_t)(PIECE_RING_WORDS - 1)][lane];
-    const uint32_t behind1 = ring[(reader.word + 4u) & (uint32_t)(PIECE_RING_WORDS - 1)][lane];
-    const uint32_t head = bits_at(reader.w0, reader.w1, reader.shift); // the next 32 bits of the stream
-    const uint32_t code = head >> 30;                                  // 0x: `0`, 2: `10`, 3: `11`
-    const bool raw = state.raw;
-    const bool opens = !raw && code == 3u, repeats = !raw && code == 2u;
-    const uint32_t header_bits = raw ? 0u : ((0x0d020101u >> (code << 3)) & 15u);
-    const uint32_t leading = (head >> 25) & 31u, length = (head >> 19) & 63u;
-    state.trailing = opens ? (32u - length - leading) & 31u : state.trailing;
-    state.window_bits = opens ? min(length, 32u) : state.window_bits;
-    const uint32_t meaningful = raw ? 32u : (repeats ? 0u : state.window_bits);
-    const uint32_t at = reader.shift + header_bits; // 0..44: where the payload begins, in bits from the top of w0
-    const bool in_first = at < 32u;
-    const uint32_t body = bits_at(in_first ? reader.w0 : reader.w1, in_first ? reader.w1 : reader.w2, at & 31u);
-    const uint32_t payload = meaningful ? body >> ((32u - meaningful) & 31u) : 0u;
-    const uint32_t bits = raw ? payload : (state.last ^ (payload << state.trailing));
-    state.last = bits;
-    state.raw = false;
-    const uint32_t end = at + meaningful; // 0..76
-    const uint32_t taken = end >> 5;      // whole words consumed: 0, 1 or 2
-    reader.shift = end & 31u;
-    reader.word += taken;
-    const uint32_t up0 = __builtin_bswap32(behind0), up1 = __builtin_bswap32(behind1);
-    const uint32_t n0 = taken == 0u ? reader.w0 : (taken == 1u ? reader.w1 : reader.w2);
-    const uint32_t n1 = taken == 0u ? reader.w1 : (taken == 1u ? reader.w2 : up0);
-    const uint32_t n2 = taken == 0u ? reader.w2 : (taken == 1u ? up0 : up1);
-    reader.w0 = n0;
-    reader.w1 = n1;
-    reader.w2 = n2;
-    return bits;
-}
-
-// The largest of the lanes' values, in every lane.
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t x) {
-#pragma unroll
-    for (int step = 1; step < MDB_WAVE; step <<= 1) x = max(x, (uint32_t)__shfl_xor((int)x, step, MDB_WAVE));
-    return x;
-}
-
 // The one kind of stream of an indexed batch that k_grid_serial keeps (see k_grid_mv_pieces).
 __device__ __forceinline__ bool mv_left_to_serial(uint32_t tile_flags) {
     return (tile_flags & FLAG_JUMPS) && (tile_flags & FLAG_TYPE_MASK) == MDB_SWING_ID;
@@ -1524,18 +1221,16 @@ __global__ __launch_bounds__(MDB_WAVE) void k_grid_mv_pieces(DevSegments s, Time
     uint32_t count = 0, skip = 0; // values of this lane's piece to write, and how many in front of them are not wanted
     unsigned long long out_at = 0;
     PieceReader reader;
-    PieceState state;
+    PieceState state = piece_state_idle();
     reader.idle(cursors);
-    state.last = 0; state.trailing = 0; state.window_bits = 0; state.raw = false;
     if (piece < n_pieces) {
-        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-        const uint32_t i = c0.z, point_index = c0.w, n_values = c1.x, window = c1.y;
+        const PieceCursor cursor = load_piece_cursor(cursors, piece);
+        const uint32_t i = cursor.segment(), point_index = cursor.point_index(), n_values = cursor.n_values();
         const TileDesc t = desc[i];
         // Cursors that host threads have left (mv_host_index) mark the last piece of every stream: it has to end where
         // this call's own analysis of the segment ends the stream, or the two disagree about the segment's length.
-        if ((c1.w & MV_CURSOR_LAST_OF_STREAM) && !range.enabled &&
-            point_index + n_values != ((window & MV_WINDOW_RESIDUAL) ? t.n_points : t.n_model))
+        if ((cursor.marks() & MV_CURSOR_LAST_OF_STREAM) && !range.enabled &&
+            point_index + n_values != (cursor.residual() ? t.n_points : t.n_model))
             atomicOr(&header->error, ERR_HOST_INDEX);
         uint32_t first = 0;
         if (range.enabled) {
@@ -1550,26 +1245,15 @@ __global__ __launch_bounds__(MDB_WAVE) void k_grid_mv_pieces(DevSegments s, Time
             skip = lo - point_index;
             count = hi - lo;
             out_at = offsets[i] + (lo - first);
-            const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
-            const DevCol &column = residual ? s.residuals : s.values;
-            const uint4 view = column.views[i];
-            const uint64_t nbytes = residual ? (uint64_t)view.x - 1u : (uint64_t)view.x;
-            reader.open(view_data(column, i, view, residual ? residuals_first : values_first), nbytes, c0.x);
+            piece_open(reader, s, cursor, values_first, residuals_first);
+            // (grid()'s seed: the model's last RECONSTRUCTED value - the descriptor's, or the cursor's behind a MacaqueV model)
             const bool macaque = (t.flags & FLAG_TYPE_MASK) == MDB_MACAQUE_V_ID;
-            state.last = (macaque ? c1.z : __float_as_uint(t.value)) ^ c0.y;
-            // (no window yet - leading 255 - is a window of no bits: the stream's first code opens one)
-            const uint32_t leading = window & 255u, trailing = (window >> 8) & 255u;
-            state.trailing = trailing & 31u;
-            state.window_bits = leading + trailing <= 32u ? 32u - leading - trailing : 0u;
-            state.raw = (window & MV_WINDOW_RAW) != 0;
+            state = piece_state(cursor, macaque ? cursor.chain_seed() : __float_as_uint(t.value));
         }
     }
     // (every lane decodes in every step, wanted or not: straight-line code; a lane that is through with its piece
     // makes values nobody looks at from bytes it may read)
-    reader.begin();
-    reader.top_up(ring, lane);
-    reader.top_up(ring, lane);
-    reader.start(ring, lane);
+    piece_start(reader, ring, lane);
     // The values in front of the wanted ones are decoded (the chain runs through them) and dropped.
     for (uint32_t k = 0, most = wave_max_u32(skip); k < most; k++) {
         if (__any(reader.hungry())) reader.top_up(ring, lane);
@@ -1639,336 +1323,6 @@ __global__ __launch_bounds__(MDB_WAVE) void k_grid_mv_pieces(DevSegments s, Time
         atomicAdd(&g_mvp_timing[5], 1ull);
     }
 #endif
-}
-
-// ---- the same cursors for SUM: macaque_v::sum adds a stream's values one after the other in f32 --------------
-//
-// f32 addition does not associate, so the additions of one stream stay a chain - but 64 chains fit into a wave, and
-// the decoding, a hundred times the work, is again one lane per piece: k_agg_mv_pieces decodes every piece of the
-// batch into scratch (piece p at values[64 p ..]: a stream's values follow each other), with the seeds sum() uses
-// (models/mod.rs:145-181: the model's last DECODED value, NaN behind a MacaqueV model), and k_agg_mv_chains adds
-// every stream up with one lane. stream_sums[2 i] = the sum of MacaqueV segment i's values (macaque_v.rs:228-235:
-// it starts AS the first value), [2 i + 1] = the sum of segment i's residual tail.
-struct ChainItem { // 16 bytes: a stream of two pieces or more, listed by the wave of k_agg_mv_pieces it begins in
-    uint32_t segment_and_kind; // segment << 1 | 1 for its residual tail
-    uint32_t n;                // its values, if it ends in the wave it begins in (0: it goes on - its segment's analysis knows)
-    unsigned long long first_piece;
-};
-
-// Is piece `piece` (of segment i's values or of its tail) the first / the last of its stream? (The pieces of a stream
-// follow each other in the cursor index.)
-__device__ __forceinline__ void piece_neighbours(const MvCursor *__restrict__ cursors, unsigned long long piece, unsigned long long n_pieces,
-                                                 uint32_t i, bool residual, bool *is_head, bool *is_tail) {
-    if (piece == 0) {
-        *is_head = true;
-    } else {
-        const MvCursor *before = cursors + piece - 1;
-        *is_head = load_global(&before->segment) != i || ((load_global(&before->window) & MV_WINDOW_RESIDUAL) != 0) != residual;
-    }
-    if (piece + 1 == n_pieces) {
-        *is_tail = true;
-    } else {
-        const MvCursor *behind = cursors + piece + 1;
-        *is_tail = load_global(&behind->segment) != i || ((load_global(&behind->window) & MV_WINDOW_RESIDUAL) != 0) != residual;
-    }
-}
-
-// Which lanes of a wave of pieces list a stream - the first pieces of streams of two pieces or more -, of which kind
-// (short: up to CHAIN_SHORT_VALUES values; long: more, or going on behind the wave, where only the segment's analysis
-// knows how many), with how many values, and the lane's place among the wave's listed streams of its kind.
-constexpr uint32_t CHAIN_SHORT_VALUES = 1024;
-struct ChainListing {
-    bool lists, is_long;
-    uint32_t n;                // values of the stream; 0: it goes on behind the wave
-    uint32_t rank;             // among the wave's listed streams of the same kind
-    uint32_t n_short, n_long;  // of the wave
-};
-__device__ __forceinline__ ChainListing chain_listing(bool present, bool is_head, bool is_tail, uint32_t to_decode, int lane) {
-    ChainListing out;
-    out.lists = present && is_head && !is_tail;
-    const unsigned long long tails = __ballot(present && is_tail);
-    const unsigned long long tails_behind = lane == 63 ? 0ull : (tails >> (lane + 1));
-    const int my_tail = tails_behind ? lane + 1 + __builtin_ctzll(tails_behind) : -1; // (none: the stream goes on behind the wave)
-    const uint32_t last_count = (uint32_t)__shfl((int)to_decode, my_tail >= 0 ? my_tail : lane, MDB_WAVE);
-    out.n = my_tail >= 0 ? (uint32_t)(my_tail - lane) * MV_PIECE_VALUES + last_count : 0u; // (64 a piece but the last)
-    out.is_long = out.n == 0u || out.n > CHAIN_SHORT_VALUES;
-    const unsigned long long shorts = __ballot(out.lists && !out.is_long), longs = __ballot(out.lists && out.is_long);
-    const unsigned long long below = (1ull << lane) - 1ull;
-    out.rank = (uint32_t)__popcll((out.is_long ? longs : shorts) & below);
-    out.n_short = (uint32_t)__popcll(shorts);
-    out.n_long = (uint32_t)__popcll(longs);
-    return out;
-}
-
-// How many streams of either kind every wave of pieces lists: long << 32 | short (the scan over these says where).
-__global__ __launch_bounds__(MDB_WAVE) void k_agg_mv_chain_count(const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
-                                                                 unsigned long long *__restrict__ counts) {
-    const int lane = threadIdx.x;
-    const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
-    bool is_head = false, is_tail = false;
-    uint32_t to_decode = 0;
-    if (piece < n_pieces) {
-        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-        to_decode = c1.x;
-        piece_neighbours(cursors, piece, n_pieces, c0.z, (c1.y & MV_WINDOW_RESIDUAL) != 0, &is_head, &is_tail);
-    }
-    const ChainListing listing = chain_listing(piece < n_pieces, is_head, is_tail, to_decode, lane);
-    if (lane == 0) counts[blockIdx.x] = ((unsigned long long)listing.n_long << 32) | listing.n_short;
-}
-struct ChainCount {
-    const unsigned long long *counts;
-    __device__ uint64_t operator()(uint64_t wave) const { return counts[wave]; }
-};
-
-// One lane per piece, as k_grid_mv_pieces (the same decoder, rounds of ROUND values staged in LDS): a piece that is a
-// whole stream - most residual tails are - is added up by its own lane while it is decoded (its values ARE the stream,
-// in order); the pieces of longer streams go to `values` (piece p at 64 p, rows of ROUND consecutive values per store)
-// and the stream is listed for k_agg_mv_chain_groups by the lane of its first piece. (Round 5's kernel staged all 64
-// values of every piece - 22 KB of LDS a wave, 1.75 waves a SIMD - so that the lane of a stream's first piece could add
-// up the stream inside the wave while the other 63 waited: 2.7 / 2.3 ms where this decoder needs 2.0 / 1.45 for grid().)
-template <int ROUND>
-__global__ __launch_bounds__(MDB_WAVE) void k_agg_mv_pieces(DevSegments s, const MvCursor *__restrict__ cursors,
-                                                            unsigned long long n_pieces, uint32_t *__restrict__ values,
-                                                            float *__restrict__ stream_sums, ChainItem *__restrict__ short_items,
-                                                            ChainItem *__restrict__ long_items,
-                                                            const unsigned long long *__restrict__ chain_offsets) {
-    constexpr int STRIDE = ROUND + 1; // (a row per lane: an odd stride keeps the banks apart)
-    __shared__ uint32_t stage[MDB_WAVE * STRIDE];
-    __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
-    __shared__ uint32_t row_count[MDB_WAVE];
-    const int lane = threadIdx.x;
-    const unsigned long long first_piece = (unsigned long long)blockIdx.x * MDB_WAVE;
-    const unsigned long long piece = first_piece + lane;
-    const uint8_t *values_first = first_buffer(s.values), *residuals_first = first_buffer(s.residuals); // (see view_data())
-    uint32_t to_decode = 0, segment = 0xffffffffu;
-    bool residual = false, is_head = false, is_tail = false;
-    PieceReader reader;
-    PieceState state;
-    reader.idle(cursors);
-    state.last = 0; state.trailing = 0; state.window_bits = 0; state.raw = false;
-    if (piece < n_pieces) {
-        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-        const uint32_t i = c0.z, window = c1.y;
-        segment = i;
-        to_decode = c1.x;
-        residual = (window & MV_WINDOW_RESIDUAL) != 0;
-        piece_neighbours(cursors, piece, n_pieces, i, residual, &is_head, &is_tail);
-        const DevCol &column = residual ? s.residuals : s.values;
-        const uint4 view = column.views[i];
-        reader.open(view_data(column, i, view, residual ? residuals_first : values_first),
-                    residual ? (uint64_t)view.x - 1u : (uint64_t)view.x, c0.x);
-        uint32_t seed = 0;
-        if (residual) {
-            const int32_t type = s.model_type_id[i];
-            if (type == MDB_PMC_MEAN_ID) {
-                float value = 0.0f;
-                (void)decode_pmc_value(s.values.views[i], s.min_value[i], s.max_value[i], &value);
-                seed = __float_as_uint(value);
-            } else if (type == MDB_SWING_ID) {
-                float first = 0.0f, last = 0.0f;
-                (void)decode_swing_values(s.values.views[i], s.min_value[i], s.max_value[i], &first, &last);
-                seed = __float_as_uint(last);
-            } else {
-                seed = 0x7fc00000u; // f32::NAN (models/mod.rs:167)
-            }
-        }
-        state.last = seed ^ c0.y;
-        const uint32_t leading = window & 255u, trailing = (window >> 8) & 255u;
-        state.trailing = trailing & 31u;
-        state.window_bits = leading + trailing <= 32u ? 32u - leading - trailing : 0u;
-        state.raw = (window & MV_WINDOW_RAW) != 0;
-    }
-    const bool present = piece < n_pieces;
-    const bool whole = present && is_head && is_tail; // the piece is its stream: summed here
-    const bool spilled = present && !whole;           // a piece of a longer stream: its values go to memory
-    // The streams of two pieces or more that begin in this wave, listed where the scan says (k_agg_mv_chain_count made
-    // the same tests): the short ones in one list, the long ones in another.
-    {
-        const ChainListing listing = chain_listing(present, is_head, is_tail, to_decode, lane);
-        if (listing.lists) {
-            const unsigned long long where = chain_offsets[blockIdx.x];
-            ChainItem *to = listing.is_long ? long_items + (where >> 32) : short_items + (where & 0xffffffffull);
-            to[listing.rank] = {(segment << 1) | (residual ? 1u : 0u), listing.n, piece};
-        }
-    }
-    reader.begin();
-    reader.top_up(ring, lane);
-    reader.top_up(ring, lane);
-    reader.start(ring, lane);
-    // macaque_v.rs:220-265: a segment's values are added to the first one, a tail's to 0, one after the other.
-    float own = 0.0f;
-    const bool starts_as_first = !residual;
-    for (uint32_t done = 0; __any(done < to_decode); done += ROUND) {
-        const uint32_t mine = done < to_decode ? min(to_decode - done, (uint32_t)ROUND) : 0u;
-        static_assert(ROUND % 2 == 0, "values are decoded in pairs");
-        for (uint32_t k = 0, most = wave_max_u32(mine); k < most; k += 2) {
-            if (__any(reader.hungry())) reader.top_up(ring, lane);
-            const uint32_t even = piece_decode_value(reader, state, ring, lane);
-            const uint32_t odd = piece_decode_value(reader, state, ring, lane);
-            stage[lane * STRIDE + k] = even;
-            stage[lane * STRIDE + k + 1] = odd; // (k + 1 == ROUND: the row's spare word)
-            // (the running sum of the lane's own piece: what a piece that is a whole stream reports)
-            const float with_even = (starts_as_first && done + k == 0u) ? __uint_as_float(even) : own + __uint_as_float(even);
-            own = k < mine ? with_even : own;
-            own = k + 1 < mine ? own + __uint_as_float(odd) : own;
-        }
-        // Row r = this round's values of lane r's piece, for the pieces that go to memory: consecutive values,
-        // (64 / ROUND) rows per store instruction.
-        row_count[lane] = spilled ? mine : 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        constexpr int ROWS_PER_STORE = MDB_WAVE / ROUND;
-        const int sub_row = lane / ROUND, column_of_lane = lane % ROUND;
-        constexpr int BATCH = 8;
-        static_assert(MDB_WAVE % (BATCH * ROWS_PER_STORE) == 0, "whole batches of stores");
-        for (int r0 = 0; r0 < MDB_WAVE; r0 += BATCH * ROWS_PER_STORE) {
-            uint32_t counts[BATCH], staged[BATCH];
-#pragma unroll
-            for (int q = 0; q < BATCH; q++) {
-                const int r = r0 + q * ROWS_PER_STORE + sub_row;
-                counts[q] = row_count[r];
-                staged[q] = stage[r * STRIDE + column_of_lane];
-            }
-#pragma unroll
-            for (int q = 0; q < BATCH; q++) {
-                const int r = r0 + q * ROWS_PER_STORE + sub_row;
-                if ((uint32_t)column_of_lane < counts[q])
-                    values[(first_piece + (unsigned long long)r) * MV_PIECE_VALUES + done + (uint32_t)column_of_lane] = staged[q];
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-    if (whole && to_decode > 0) stream_sums[2ull * segment + (residual ? 1u : 0u)] = own;
-}
-
-// A stream of two pieces or more: its values lie in `values` (piece p at 64 p), and its f32 additions are one chain,
-// in stream order (macaque_v.rs:228-235). A chain is 4 cycles an addition; what it waited for was memory - a lane of
-// its own kept 128 bytes of its stream in flight, a round trip per 32 additions (round 6's counters: 65 % of the
-// kernel's wave-cycles waiting, the vector ALU busy 5 %; a 65 536-value stream 0.7 ms) - and, in front of that, a thread
-// per SEGMENT that looked for the streams not summed yet (0.75 ms for 8.5 M segments). Now the waves of k_agg_mv_pieces
-// list the streams that begin in them (k_agg_mv_chain_count + a scan say where), and k_agg_mv_chain_groups gives every
-// listed stream EIGHT lanes: together they keep 2 KB of it in flight - a round of 512 values, 16 chunks of 16 bytes per
-// lane, the eight lanes' chunks side by side in memory - park a round in LDS, ask for the next one, and the first of
-// the eight adds the parked round up, value after value.
-// Two sizes of round: most listed streams are a few pieces long (a stretch of rejected points between two models) and
-// want many waves in flight more than bytes - 4 loads a lane, 128 values a round, 4 KB of LDS a wave; the long ones
-// (a whole chunk of noise is one stream of 65 536 values) want the bytes - 16 loads a lane, 512 values a round. A list
-// of its own for each kind (a stream that goes on behind its wave counts as long): the long chains begin at once
-// instead of behind the dispatch of the short ones' hundred thousand waves.
-constexpr int CHAIN_GROUP_LANES = 8;
-constexpr int CHAIN_GROUPS_PER_WAVE = MDB_WAVE / CHAIN_GROUP_LANES;
-
-// Cursors left by host threads (the index of one call): should they ever disagree with the kernels' own analysis about
-// a segment's streams, its sums are made unusable rather than a little wrong. (A resident batch's cursors come from
-// that same analysis, k_mv_index_walk: nothing to compare.)
-__global__ __launch_bounds__(256) void k_agg_mv_check_cursors(DevSegments s, const uint32_t *__restrict__ known_totals,
-                                                              const unsigned long long *__restrict__ piece_base,
-                                                              float *__restrict__ stream_sums) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= s.n) return;
-    const unsigned long long first_piece = piece_base[i];
-    if (piece_base[i + 1] == first_piece) return; // (no stream: nobody reads this segment's sums)
-    uint32_t n_values, n_res, n_model, error;
-    mv_stream_lengths(s, i, known_totals, &n_values, &n_res, &n_model, &error);
-    if ((unsigned long long)((n_values + MV_PIECE_VALUES - 1) / MV_PIECE_VALUES + (n_res + MV_PIECE_VALUES - 1) / MV_PIECE_VALUES) !=
-        piece_base[i + 1] - first_piece)
-        stream_sums[2 * i] = stream_sums[2 * i + 1] = __uint_as_float(0x7fc00000u);
-}
-
-template <int CHAIN_LOADS> // 16-byte loads a lane has in flight: 4 for the list of short streams, 16 for the long ones
-__global__ __launch_bounds__(MDB_WAVE) void k_agg_mv_chain_groups(DevSegments s, const uint32_t *__restrict__ known_totals,
-                                                                  const uint32_t *__restrict__ values, float *__restrict__ stream_sums,
-                                                                  const ChainItem *__restrict__ items, unsigned int n_items) {
-    constexpr int CHAIN_ROUND_CHUNKS = CHAIN_LOADS * CHAIN_GROUP_LANES; // chunks of 16 bytes = 4 values a round
-    constexpr int CHAIN_GROUP_STRIDE = CHAIN_ROUND_CHUNKS + 1;          // (in chunks: the eight adding lanes read eight banks)
-    __shared__ uint4 parked[CHAIN_GROUPS_PER_WAVE * CHAIN_GROUP_STRIDE];
-    const int lane = threadIdx.x, group = lane / CHAIN_GROUP_LANES, member = lane % CHAIN_GROUP_LANES;
-    const unsigned int mine = blockIdx.x * CHAIN_GROUPS_PER_WAVE + (unsigned int)group;
-    const bool listed = mine < n_items;
-    ChainItem item{0u, 1u, 0ull}; // (a group without a stream: one value of the scratch's first piece, nobody's sum)
-    if (listed) item = items[mine];
-    // How many values the stream has: its pieces said so if it ended in the wave it began in, else the analysis of
-    // its segment, by the group's first lane.
-    uint32_t n = item.n;
-    const bool tail = (item.segment_and_kind & 1u) != 0u;
-    if (listed && member == 0 && n == 0) {
-        uint32_t n_values, n_res, n_model, error;
-        mv_stream_lengths(s, item.segment_and_kind >> 1, known_totals, &n_values, &n_res, &n_model, &error);
-        n = tail ? n_res : n_values;
-    }
-    n = (uint32_t)__shfl((int)n, group * CHAIN_GROUP_LANES, MDB_WAVE);
-    const uint32_t n_chunks = (n + 3u) >> 2;
-    const uint4 *__restrict__ from = reinterpret_cast<const uint4 *>(values + item.first_piece * MV_PIECE_VALUES);
-    uint4 *mine_parked = parked + group * CHAIN_GROUP_STRIDE;
-    auto ask = [&](uint32_t round, uint4 (&into)[CHAIN_LOADS]) { // chunk j * 8 + member of the round: the group's lanes side by side
-#pragma unroll
-        for (int j = 0; j < CHAIN_LOADS; j++) {
-            const uint32_t chunk = round * CHAIN_ROUND_CHUNKS + (uint32_t)(j * CHAIN_GROUP_LANES + member);
-            into[j] = chunk < n_chunks ? load_global(from + chunk) : make_uint4(0u, 0u, 0u, 0u);
-        }
-    };
-    auto wave_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const uint32_t rounds = (n_chunks + CHAIN_ROUND_CHUNKS - 1) / CHAIN_ROUND_CHUNKS;
-    const uint32_t most_rounds = wave_max_u32(rounds);
-    // macaque_v.rs:228-235: the sum of a MacaqueV segment's values starts AS the first of them, a tail's at zero.
-    const bool starts_as_first = !tail;
-    float sum = 0.0f;
-    uint4 asked[CHAIN_LOADS];
-    ask(0, asked);
-    for (uint32_t round = 0; round < most_rounds; round++) {
-#pragma unroll
-        for (int j = 0; j < CHAIN_LOADS; j++) mine_parked[j * CHAIN_GROUP_LANES + member] = asked[j];
-        wave_sync();
-        if (round + 1 < most_rounds) ask(round + 1, asked); // (under way while the round that is parked is added up)
-        if (member == 0 && round < rounds) {
-            const uint32_t first_value = round * (uint32_t)(4 * CHAIN_ROUND_CHUNKS);
-            const uint32_t here = min(n - first_value, (uint32_t)(4 * CHAIN_ROUND_CHUNKS)); // values of this round
-            uint32_t k = 0;
-            if (round == 0 && starts_as_first) {
-                const uint4 q = mine_parked[0];
-                sum = __uint_as_float(q.x);
-                if (here > 1) sum += __uint_as_float(q.y);
-                if (here > 2) sum += __uint_as_float(q.z);
-                if (here > 3) sum += __uint_as_float(q.w);
-                k = 4;
-            }
-            for (; k + 32 <= here; k += 32) { // (eight reads of the parked round under way, then the chain of additions;
-                                              // the next batch's reads under way during the additions: slower, 0.77 -> 0.92 ms)
-                uint4 q[8];
-#pragma unroll
-                for (int j = 0; j < 8; j++) q[j] = mine_parked[(k >> 2) + (uint32_t)j];
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    sum += __uint_as_float(q[j].x);
-                    sum += __uint_as_float(q[j].y);
-                    sum += __uint_as_float(q[j].z);
-                    sum += __uint_as_float(q[j].w);
-                }
-            }
-            for (; k + 4 <= here; k += 4) {
-                const uint4 q = mine_parked[k >> 2];
-                sum += __uint_as_float(q.x);
-                sum += __uint_as_float(q.y);
-                sum += __uint_as_float(q.z);
-                sum += __uint_as_float(q.w);
-            }
-            if (k < here) { // (the stream's last, partial chunk)
-                const uint4 q = mine_parked[k >> 2];
-                sum += __uint_as_float(q.x);
-                if (k + 1 < here) sum += __uint_as_float(q.y);
-                if (k + 2 < here) sum += __uint_as_float(q.z);
-            }
-        }
-        wave_sync(); // (the next round overwrites what was parked)
-    }
-    if (member == 0 && listed && n > 0) stream_sums[2ull * (item.segment_and_kind >> 1) + (tail ? 1u : 0u)] = sum;
 }
 
 // ---- the order in which k_grid_ts_count takes the streams ----------------------------------------------------
@@ -2907,6 +2261,7 @@ __global__ __launch_bounds__(TS_THREADS) void k_grid_timestamps_left(TsWaveArgs 
     }
 }
 
+// The serial kernel (MacaqueV streams out of the ring of mdb_mv_pieces.hpp; irregular timestamps keep the direct reader).
 __global__ __launch_bounds__(SERIAL_THREADS) void k_grid_serial(
     DevSegments s, TimeRange range, const unsigned long long *__restrict__ offsets,
     const uint32_t *__restrict__ serial_ids, uint64_t n_serial, const MvSeg *__restrict__ mv_segs,
@@ -3288,15 +2643,18 @@ int ts_range_from_kept(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &
 thread_local std::shared_ptr<MvIndex> t_call_index;
 thread_local const void *t_call_index_views = nullptr;
 
+// The batch's index as it stands, nothing built: the one of this call's own upload (built and usable as it is made),
+// else the one a resident batch keeps; none with MDB_GRID_MV_INDEX=0.
+std::shared_ptr<MvIndex> mv_index_lookup(const mdb_segments *in) {
+    const char *setting = option_text("MDB_GRID_MV_INDEX");
+    if (setting && std::strcmp(setting, "0") == 0) return nullptr;
+    if (t_call_index && t_call_index_views == in->values.views) return t_call_index;
+    return owned_segments_index(in);
+}
+
 int mv_index_prepare(mdb_ctx *ctx, const mdb_segments *in, std::shared_ptr<MvIndex> *out) {
     out->reset();
-    const char *setting = option_text("MDB_GRID_MV_INDEX");
-    if (setting && std::strcmp(setting, "0") == 0) return 0;
-    if (t_call_index && t_call_index_views == in->values.views) {
-        *out = t_call_index;
-        return 0;
-    }
-    std::shared_ptr<MvIndex> index = owned_segments_index(in);
+    std::shared_ptr<MvIndex> index = mv_index_lookup(in);
     if (!index) return 0;
     std::lock_guard<std::mutex> lock(index->mutex);
     if (!index->built) {
@@ -3338,116 +2696,6 @@ int mv_index_prepare(mdb_ctx *ctx, const mdb_segments *in, std::shared_ptr<MvInd
         index->built = true;
     }
     if (index->usable) *out = index;
-    return 0;
-}
-
-// For mdb_agg.hip: the f32 sums of all MacaqueV streams of a batch that has a cursor index (see k_agg_mv_pieces);
-// *stream_sums stays nullptr when it has none. known_totals: of the caller's own counting walk (may be nullptr).
-int mv_index_stream_sums(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const uint32_t *known_totals,
-                         const float **stream_sums, const unsigned long long **only_with_pieces) {
-    *stream_sums = nullptr;
-    *only_with_pieces = nullptr;
-    const char *setting = option_text("MDB_GRID_MV_INDEX");
-    if (setting && std::strcmp(setting, "0") == 0) return 0;
-    const bool of_this_call = t_call_index && t_call_index_views == in->values.views;
-    std::shared_ptr<MvIndex> index = of_this_call ? t_call_index : owned_segments_index(in);
-    if (!index) return 0;
-    {
-        std::lock_guard<std::mutex> lock(index->mutex);
-        if (!index->built || !index->usable) return 0; // (built by the first grid call, or by agg_run before its own walk)
-    }
-    // (the index of one call covers its long streams only: the sums of a segment without pieces are nobody's)
-    if (index->of_one_call) *only_with_pieces = static_cast<const unsigned long long *>(index->piece_base);
-    const uint64_t piece_waves = (index->n_pieces + MDB_WAVE - 1) / MDB_WAVE;
-    if (piece_waves > 0x7ffffff0ull) return fail("Too many MacaqueV streams for one batch.");
-    // (every listed stream has two pieces or more)
-    const uint64_t most_items = index->n_pieces / 2 + 1;
-    const uint64_t counts_bytes = align_up(piece_waves * 8, 256), offsets_bytes = align_up((piece_waves + 1) * 8, 256);
-    const uint64_t block_sums_bytes = align_up(scan_block_sums_bytes(piece_waves), 256);
-    void *p = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_AGG_MV, index->n_pieces * MV_PIECE_VALUES * 4 + in->n * 8 + 256, &p)) return 1;
-    uint32_t *values = static_cast<uint32_t *>(p);
-    float *sums = reinterpret_cast<float *>(values + index->n_pieces * MV_PIECE_VALUES);
-    // (a stream without values - the tail of a segment that has none - sums to 0: the kernels write the others)
-    MDB_HIP_CHECK(hipMemsetAsync(sums, 0, 8 * in->n, ctx->stream));
-    void *q = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_AGG_CHAIN_LIST, counts_bytes + offsets_bytes + block_sums_bytes + 2 * most_items * sizeof(ChainItem) + 64, &q)) return 1;
-    uint8_t *at = static_cast<uint8_t *>(q);
-    unsigned long long *counts = reinterpret_cast<unsigned long long *>(at);
-    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(at + counts_bytes);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(at + counts_bytes + offsets_bytes);
-    ChainItem *short_items = reinterpret_cast<ChainItem *>(at + counts_bytes + offsets_bytes + block_sums_bytes);
-    ChainItem *long_items = short_items + most_items;
-    const MvCursor *cursors = static_cast<const MvCursor *>(index->cursors);
-    // Where every wave of pieces lists the streams of two pieces or more that begin in it: a function of the cursors
-    // alone, so the index of a resident batch keeps it from the first call that asks (MDB_AGG_KEEP_CHAIN_OFFSETS=0:
-    // counted by every call, as the index of one call over host batches is).
-    unsigned long long listed = 0;
-    bool counted_before = false;
-    const char *keep_setting = option_text("MDB_AGG_KEEP_CHAIN_OFFSETS");
-    const bool keep = !index->of_one_call && !(keep_setting && std::strcmp(keep_setting, "0") == 0);
-    if (keep) {
-        std::lock_guard<std::mutex> lock(index->mutex);
-        if (index->chains_built) {
-            offsets = static_cast<unsigned long long *>(index->chain_offsets);
-            listed = index->chains_listed;
-            counted_before = true;
-        }
-    }
-    if (!counted_before) {
-        void *kept = nullptr;
-        if (keep && hipMalloc(&kept, (piece_waves + 1) * 8) != hipSuccess) { // (no memory to keep it in: counted every time)
-            (void)hipGetLastError();
-            kept = nullptr;
-        }
-        if (kept) offsets = static_cast<unsigned long long *>(kept);
-        {
-            LaunchTimer timer(ctx, "k_agg_mv_chain_count");
-            hipLaunchKernelGGL(k_agg_mv_chain_count, dim3((uint32_t)piece_waves), dim3(MDB_WAVE), 0, ctx->stream, cursors, index->n_pieces, counts);
-        }
-        int failed = device_exclusive_scan(ctx, ChainCount{counts}, piece_waves, offsets, block_sums, "k_agg_mv_chain_scan");
-        // (how many are listed sizes the launches behind the piece kernel: a wave that finds nothing to do still costs a
-        // third of a microsecond, and the most there can be is 5.4 M groups for the mixed series' 10.8 M pieces)
-        if (!failed && (mail_read(ctx, &listed, offsets + piece_waves, 8) != hipSuccess || mail_sync(ctx) != hipSuccess))
-            failed = fail("Could not read how many MacaqueV streams the pieces list.");
-        if (failed) {
-            if (kept) (void)hipFree(kept);
-            return 1;
-        }
-        if (kept) { // (complete: the stream has been waited for) - unless another context's call has left its own meanwhile
-            std::lock_guard<std::mutex> lock(index->mutex);
-            if (!index->chains_built) {
-                index->chain_offsets = kept;
-                index->chains_listed = listed;
-                index->chains_built = true;
-                kept = nullptr;
-            } else {
-                offsets = static_cast<unsigned long long *>(index->chain_offsets);
-            }
-        }
-        if (kept) MDB_HIP_CHECK(hipFree(kept));
-    }
-    const uint64_t n_short = listed & 0xffffffffull, n_long = listed >> 32;
-    if (n_short > most_items || n_long > most_items) return fail("Internal error: more MacaqueV streams listed than there are pieces for.");
-    {
-        LaunchTimer timer(ctx, "k_agg_mv_pieces");
-        hipLaunchKernelGGL(k_agg_mv_pieces<32>, dim3((uint32_t)piece_waves), dim3(MDB_WAVE), 0, ctx->stream, s, cursors, index->n_pieces,
-                           values, sums, short_items, long_items, static_cast<const unsigned long long *>(offsets));
-    }
-    {
-        // The listed streams, eight lanes each: the long kind first (they are what takes longest), the short kind behind.
-        LaunchTimer timer(ctx, "k_agg_mv_chains");
-        if (n_long > 0)
-            hipLaunchKernelGGL((k_agg_mv_chain_groups<16>), dim3((uint32_t)((n_long + CHAIN_GROUPS_PER_WAVE - 1) / CHAIN_GROUPS_PER_WAVE)),
-                               dim3(MDB_WAVE), 0, ctx->stream, s, known_totals, values, sums, long_items, (unsigned int)n_long);
-        if (n_short > 0)
-            hipLaunchKernelGGL((k_agg_mv_chain_groups<4>), dim3((uint32_t)((n_short + CHAIN_GROUPS_PER_WAVE - 1) / CHAIN_GROUPS_PER_WAVE)),
-                               dim3(MDB_WAVE), 0, ctx->stream, s, known_totals, values, sums, short_items, (unsigned int)n_short);
-        if (index->of_one_call)
-            hipLaunchKernelGGL(k_agg_mv_check_cursors, dim3((uint32_t)((in->n + 255) / 256)), dim3(256), 0, ctx->stream, s, known_totals,
-                               static_cast<const unsigned long long *>(index->piece_base), sums);
-    }
-    *stream_sums = sums;
     return 0;
 }
 
@@ -3667,99 +2915,21 @@ void fill_metrics(const GridHeader &h, mdb_grid_metrics *m) {
     m->segments_irregular = h.metrics[8];
 }
 
-// The parallel decoder (mdb_macaque_parallel.hpp) over n_serial candidate streams holding stream_bytes
-// bytes between them: `select` launches the kernel that fills segs[0..n_serial), the decoded values go
-// to out_val + MvSeg::out_offset and MvSeg::done says which streams were decoded. *segs_out stays
-// nullptr when the batch has so many streams that one lane per stream is the better plan.
-template <typename Select>
-int mv_pipeline(mdb_ctx *ctx, uint64_t n_serial, uint64_t stream_bytes, bool forced, Select select, float *out_val,
-                unsigned int *error, MvSeg **segs_out) {
-    // Every qualifying stream has ceil(bits / MV_PIECE_BITS) pieces.
-    const uint64_t max_pieces = stream_bytes * 8 / MV_PIECE_BITS + n_serial + 1;
-    if (max_pieces > MV_MAX_PIECES && !forced) return 0; // enough streams for one lane per stream
-    if (max_pieces * MV_CHAINS > 0x7fffff00ull) return 0;
-    const uint64_t sums_bytes = scan_block_sums_bytes(n_serial);
-    const uint64_t segs_bytes = align_up(n_serial * sizeof(MvSeg), 256);
-    const uint64_t base_bytes = align_up((n_serial + 1) * 8, 256) + align_up(sums_bytes, 256);
-    const uint64_t heads_bytes = align_up(max_pieces * MV_CHAINS * MV_HEAD * sizeof(MvRec), 256);
-    const uint64_t chains_bytes = align_up(max_pieces * MV_CHAINS * sizeof(MvChain), 256);
-    const uint64_t links_bytes = align_up(max_pieces * MV_CHAINS * sizeof(MvLink), 256);
-    const uint64_t starts_bytes = align_up(max_pieces * sizeof(MvStart), 256);
-    const uint64_t guesses_bytes = 2 * align_up(max_pieces * 4, 256) + 256; // guesses + tried + pending
-    void *p = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_MV, segs_bytes + base_bytes + heads_bytes + chains_bytes + links_bytes +
-                                            starts_bytes + guesses_bytes, &p))
-        return 1;
-    uint8_t *at = static_cast<uint8_t *>(p);
-    MvSeg *segs = reinterpret_cast<MvSeg *>(at);
-    at += segs_bytes;
-    unsigned long long *piece_base = reinterpret_cast<unsigned long long *>(at);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(at + align_up((n_serial + 1) * 8, 256));
-    at += base_bytes;
-    MvRec *heads = reinterpret_cast<MvRec *>(at);
-    at += heads_bytes;
-    MvChain *chains = reinterpret_cast<MvChain *>(at);
-    at += chains_bytes;
-    MvLink *links = reinterpret_cast<MvLink *>(at);
-    at += links_bytes;
-    MvStart *starts = reinterpret_cast<MvStart *>(at);
-    at += starts_bytes;
-    uint32_t *guesses = reinterpret_cast<uint32_t *>(at);
-    uint32_t *tried = reinterpret_cast<uint32_t *>(at + align_up(max_pieces * 4, 256));
-    uint32_t *pending = reinterpret_cast<uint32_t *>(at + 2 * align_up(max_pieces * 4, 256));
-    MDB_HIP_CHECK(hipMemsetAsync(pending, 0, 256, ctx->stream));
-    MDB_HIP_CHECK(hipMemsetAsync(starts, 0, starts_bytes, ctx->stream));
-    select(segs);
-    if (device_exclusive_scan(ctx, MvPieceCount{segs}, n_serial, piece_base, block_sums, "k_mv_scan")) return 1;
-    const uint32_t piece_blocks = (uint32_t)((max_pieces + MDB_WAVE - 1) / MDB_WAVE);
-    // A wave that stages whole pieces takes 38 KB of LDS, so four of them fill a CU: beyond the
-    // 1 024 waves that are resident at once, less staging and more waves is the better trade
-    // (16 streams of 65 536 values: 5.8 / 5.95 / 6.0 ms with whole / half / quarter pieces staged;
-    // 64 streams: 7.3 / 6.85 / 6.95 ms; 256 streams: 17.0 / 14.7 / 13.8 ms).
-    const int staging = max_pieces <= 12288 ? 0 : (max_pieces <= 49152 ? 1 : 2);
-    for (int round = 0; round < MV_ROUNDS; round++) {
-        if (mv_round_kind(round) == MV_ROUND_GUESS) {
-            LaunchTimer timer(ctx, "k_mv_guess");
-            hipLaunchKernelGGL(k_mv_guess, dim3((uint32_t)n_serial), dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               piece_base, chains, guesses);
-        }
-        LaunchTimer timer(ctx, round == 0 ? "k_mv_chains_start" : (round == 1 ? "k_mv_chains_first" : "k_mv_chains_more"));
-        const dim3 chain_grid((uint32_t)((max_pieces * MV_CHAINS + MDB_WAVE - 1) / MDB_WAVE));
-        if (staging == 0)
-            hipLaunchKernelGGL(k_mv_chains<MV_STAGE_WORDS>, chain_grid, dim3(MDB_WAVE), 0, ctx->stream, segs, piece_base,
-                               n_serial, round, guesses, tried, pending, heads, chains);
-        else if (staging == 1)
-            hipLaunchKernelGGL(k_mv_chains<MV_STAGE_WORDS_HALF>, chain_grid, dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               piece_base, n_serial, round, guesses, tried, pending, heads, chains);
-        else
-            hipLaunchKernelGGL(k_mv_chains<MV_STAGE_WORDS_QUARTER>, chain_grid, dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               piece_base, n_serial, round, guesses, tried, pending, heads, chains);
-    }
-    {
-        LaunchTimer timer(ctx, "k_mv_links");
-        const uint32_t chain_blocks = (uint32_t)((max_pieces * MV_CHAINS + MDB_WAVE - 1) / MDB_WAVE);
-        hipLaunchKernelGGL(k_mv_links, dim3(chain_blocks), dim3(MDB_WAVE), 0, ctx->stream, segs, piece_base,
-                           n_serial, heads, chains, links);
-    }
-    {
-        LaunchTimer timer(ctx, "k_mv_walk");
-        hipLaunchKernelGGL(k_mv_walk, dim3((uint32_t)n_serial), dim3(MDB_WAVE), 0, ctx->stream, segs, piece_base,
-                           chains, links, starts);
-    }
-    {
-        LaunchTimer timer(ctx, "k_mv_decode");
-        if (staging == 0)
-            hipLaunchKernelGGL(k_mv_decode<MV_STAGE_WORDS>, dim3(piece_blocks), dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               piece_base, n_serial, starts, out_val, error);
-        else if (staging == 1)
-            hipLaunchKernelGGL(k_mv_decode<MV_STAGE_WORDS_HALF>, dim3(piece_blocks), dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               piece_base, n_serial, starts, out_val, error);
-        else
-            hipLaunchKernelGGL(k_mv_decode<MV_STAGE_WORDS_QUARTER>, dim3(piece_blocks), dim3(MDB_WAVE), 0, ctx->stream,
-                               segs, piece_base, n_serial, starts, out_val, error);
-    }
-    *segs_out = segs;
-    return 0;
+// ---- k_mv_select: one lane per entry of the serial list -----------------------------------------------
+
+__global__ __launch_bounds__(256) void k_mv_select(DevSegments s, TimeRange range,
+                                                   const unsigned long long *__restrict__ offsets,
+                                                   const uint32_t *__restrict__ serial_ids, uint64_t n_serial,
+                                                   uint32_t min_values, MvSeg *__restrict__ segs,
+                                                   const unsigned long long *__restrict__ indexed_piece_base) {
+    const uint64_t slot = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n_serial) return;
+    const uint32_t i = serial_ids[slot];
+    SegInfo info = analyse_segment(s, i);
+    if (range.enabled) apply_time_range(s, i, info, range);
+    // (a segment the call's cursor index has pieces for is k_grid_mv_pieces': never long enough for this decoder)
+    const bool indexed = indexed_piece_base != nullptr && indexed_piece_base[i + 1] > indexed_piece_base[i];
+    segs[slot] = mv_describe(s, i, info, indexed ? 0xffffffffu : min_values, offsets[i]);
 }
 
 // The long MacaqueV streams of a grid batch; runs after k_grid_tiles and before k_grid_serial, which
@@ -3767,7 +2937,7 @@ int mv_pipeline(mdb_ctx *ctx, uint64_t n_serial, uint64_t stream_bytes, bool for
 int grid_parallel_macaque(mdb_ctx *ctx, const DevSegments &s, TimeRange range, GridPlan &plan, float *out_val,
                           MvSeg **segs_out) {
     const uint64_t n_serial = plan.host_header.n_serial;
-    auto select = [&](MvSeg *segs) {
+    const auto select = [&](MvSeg *segs) {
         LaunchTimer timer(ctx, "k_mv_select");
         const MvIndex *index = plan.mv_index.get();
         hipLaunchKernelGGL(k_mv_select, dim3((uint32_t)((n_serial + 255) / 256)), dim3(256), 0, ctx->stream, s,
@@ -3779,675 +2949,14 @@ int grid_parallel_macaque(mdb_ctx *ctx, const DevSegments &s, TimeRange range, G
                        &plan.header->error, segs_out);
 }
 
-// ---- SUM over long MacaqueV streams (for mdb_agg.hip) ------------------------------------------------
-//
-// macaque_v::sum (macaque_v.rs:220-265) adds the values of a stream one after the other in f32, and
-// f32 addition does not associate, so the additions stay with one lane per stream. What need not stay
-// there is the decoding, which is a hundred times the work: k_agg_segments leaves the streams that
-// qualify for the parallel decoder aside, they are decoded into scratch memory here, and k_mv_sums
-// then only has to add floats.
-
-constexpr unsigned long long DEFERRED_ONE = 1ull << 40; // scan item: streams above bit 40, their values below
-
-struct DeferredItem {
-    DevSegments s;
-    uint32_t min_values;
-    TimeRange range;
-    const unsigned long long *by_pieces; // (under a time range: the index whose segments k_agg_mv_range takes, or nullptr)
-    __device__ uint64_t operator()(uint64_t i) const {
-        if (s.model_type_id[i] != MDB_MACAQUE_V_ID) return 0;
-        const SegInfo info = analyse_segment(s, i);
-        if (by_pieces && by_pieces[i + 1] > by_pieces[i] && mv_range_by_pieces(s, i, info)) return 0;
-        const uint32_t values = mv_deferred_values(s, i, info, min_values, range);
-        return values ? (DEFERRED_ONE | values) : 0;
-    }
-};
-
-__global__ __launch_bounds__(256) void k_mv_select_scanned(DevSegments s, TimeRange range,
-                                                           const unsigned long long *__restrict__ scan,
-                                                           uint32_t min_values, MvSeg *__restrict__ segs) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= s.n) return;
-    const unsigned long long mine = scan[i];
-    if ((scan[i + 1] >> 40) == (mine >> 40)) return; // not one of the streams left aside
-    SegInfo info = analyse_segment(s, i);
-    if (range.enabled) apply_time_range(s, i, info, range);
-    segs[mine >> 40] = mv_describe(s, i, info, min_values, mine & (DEFERRED_ONE - 1));
-}
-
-struct DeferredResult {
-    double sum;
-    long long count; // the three below: time-range aggregates only
-    float min;
-    float max;
-    unsigned int error;
-    unsigned int pad;
-};
-
-// What one stream contributes to a time-range aggregate.
-struct RangePartial {
-    double sum;
-    long long count;
-    float min;
-    float max;
-    __device__ __forceinline__ void clear() {
-        sum = 0.0;
-        count = 0;
-        min = FLT_MAX;
-        max = -FLT_MAX;
-    }
-    __device__ __forceinline__ void point(float v) {
-        sum += (double)v;
-        count += 1;
-        min = min_num(min, v);
-        max = max_num(max, v);
-    }
-    __device__ __forceinline__ void merge(const RangePartial &other) {
-        sum += other.sum;
-        count += other.count;
-        min = min_num(min, other.min);
-        max = max_num(max, other.max);
-    }
-};
-
-// One wave per stream. The additions are a dependent chain that only one lane can walk, so the wave's
-// job is to keep that lane fed: all lanes fetch the next MV_SUM_CHUNK values (coalesced, in flight
-// while lane 0 adds up the chunk before) and hand them over through LDS.
-constexpr uint32_t MV_SUM_CHUNK = 1024;
-
-__global__ __launch_bounds__(MDB_WAVE) void k_mv_sums(const MvSeg *__restrict__ segs, uint64_t n_slots,
-                                                      const float *__restrict__ values, float *__restrict__ sums,
-                                                      DeferredResult *__restrict__ result) {
-    __shared__ float4 chunk_lds[2][MV_SUM_CHUNK / 4];
-    const uint32_t slot = blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const MvSeg seg = segs[slot];
-    if (!seg.done) {
-        // The parallel decoder gave this stream up: decode it here, one lane.
-        if (lane != 0) return;
-        float sum = 0.0f;
-        uint32_t error = 0;
-        decode_macaque_v(reinterpret_cast<const uint8_t *>(seg.words) + seg.bias_bits / 8, seg.total_bits / 8,
-                         seg.n_model, false, 0, &error, [&](uint32_t k, uint32_t bits) {
-                             if (k == 0) sum = __uint_as_float(bits);
-                             else sum += __uint_as_float(bits);
-                         });
-        if (error) atomicOr(&result->error, error);
-        sums[slot] = sum;
-        return;
-    }
-    constexpr uint32_t PER_LANE = MV_SUM_CHUNK / MDB_WAVE;
-    const float *__restrict__ v = values + seg.out_offset;
-    const uint32_t n = seg.n_model;
-    float fetched[PER_LANE];
-    auto fetch = [&](uint32_t base) {
-#pragma unroll
-        for (uint32_t j = 0; j < PER_LANE; j++) {
-            const uint32_t k = base + j * MDB_WAVE + lane;
-            fetched[j] = k < n ? v[k] : 0.0f;
-        }
-    };
-    auto hand_over = [&](uint32_t buffer) {
-        float *to = reinterpret_cast<float *>(chunk_lds[buffer]);
-#pragma unroll
-        for (uint32_t j = 0; j < PER_LANE; j++) to[j * MDB_WAVE + lane] = fetched[j];
-    };
-    fetch(0);
-    hand_over(0);
-    __syncthreads();
-    float sum = 0.0f;
-    uint32_t buffer = 0;
-    for (uint32_t base = 0; base < n; base += MV_SUM_CHUNK, buffer ^= 1u) {
-        const bool more = base + MV_SUM_CHUNK < n;
-        if (more) fetch(base + MV_SUM_CHUNK);
-        if (lane == 0) {
-            const uint32_t count = min(MV_SUM_CHUNK, n - base);
-            const float4 *from = chunk_lds[buffer];
-            uint32_t k = 0;
-            if (base == 0) { // the sum starts AS the first value (macaque_v.rs:228-235)
-                const float *first = reinterpret_cast<const float *>(from);
-                sum = first[0];
-                for (k = 1; k < 4 && k < count; k++) sum += first[k];
-            }
-#pragma unroll 4
-            for (; k + 4 <= count; k += 4) {
-                const float4 q = from[k / 4];
-                sum += q.x;
-                sum += q.y;
-                sum += q.z;
-                sum += q.w;
-            }
-            const float *rest = reinterpret_cast<const float *>(from);
-            for (; k < count; k++) sum += rest[k];
-        }
-        if (more) hand_over(buffer ^ 1u);
-        __syncthreads();
-    }
-    if (lane == 0) sums[slot] = sum;
-}
-
-// The same sums when there are too many streams for the parallel decoder to pay off: one lane per
-// stream decodes (LDS ring, as k_grid_serial) and adds as it goes.
-__global__ __launch_bounds__(SERIAL_THREADS) void k_mv_serial_sums(const MvSeg *__restrict__ segs, uint64_t n_slots,
-                                                                  float *__restrict__ sums,
-                                                                  DeferredResult *__restrict__ result) {
-    __shared__ uint32_t ring[SERIAL_RING_WORDS][MDB_WAVE];
-    const int lane = threadIdx.x;
-    const uint64_t slot = (uint64_t)blockIdx.x * SERIAL_THREADS + lane;
-    bool active = slot < n_slots;
-    RingBitReader reader;
-    reader.begin(nullptr, 0);
-    MacaqueStream stream;
-    stream.remaining = 0; stream.position = 0; stream.last = 0;
-    stream.leading = 255; stream.trailing = 0; stream.first_is_raw = true; stream.fresh = true;
-    if (active) {
-        const MvSeg seg = segs[slot];
-        reader.begin(reinterpret_cast<const uint8_t *>(seg.words) + seg.bias_bits / 8, seg.total_bits / 8);
-        stream.remaining = seg.n_model;
-        active = seg.n_model > 0 && seg.total_bits > 0;
-    }
-    float sum = 0.0f;
-    uint32_t error = 0;
-    while (__any(active)) {
-        if (__any(active && reader.hungry())) ring_top_up(reader, ring, lane, active);
-        if (active) {
-            const bool first = stream.first_is_raw;
-            bool malformed;
-            const float value = __uint_as_float(ring_decode_value(reader, stream, ring, lane, &malformed));
-            sum = first ? value : sum + value; // the sum starts AS the first value (macaque_v.rs:228-235)
-            stream.remaining -= 1;
-            // A stream shorter than its segment claims ends the loop too: it is bounded by the bits
-            // there are, not by a (possibly corrupted) count.
-            if (malformed || reader.overrun()) error |= ERR_BITSTREAM;
-            if (malformed || reader.overrun() || stream.remaining == 0) active = false;
-        }
-    }
-    if (slot < n_slots) sums[slot] = sum;
-    if (error) atomicOr(&result->error, error);
-}
-
-constexpr int MV_FINISH_THREADS = 1024;
-
-// ---- the same for aggregates under a time range: SUM (f64), COUNT, MIN, MAX of the visible values ----------
-
-__device__ __forceinline__ RangePartial shfl_down_partial(const RangePartial &p, int delta) {
-    RangePartial q;
-    const unsigned long long sum_bits = (unsigned long long)__double_as_longlong(p.sum);
-    q.sum = __longlong_as_double((long long)(((unsigned long long)__shfl_down((uint32_t)(sum_bits >> 32), delta, MDB_WAVE) << 32) |
-                                             __shfl_down((uint32_t)sum_bits, delta, MDB_WAVE)));
-    q.count = (long long)(((unsigned long long)__shfl_down((uint32_t)((unsigned long long)p.count >> 32), delta, MDB_WAVE) << 32) |
-                          __shfl_down((uint32_t)p.count, delta, MDB_WAVE));
-    q.min = __shfl_down(p.min, delta, MDB_WAVE);
-    q.max = __shfl_down(p.max, delta, MDB_WAVE);
-    return q;
-}
-
-// One wave per stream the parallel decoder has put into `values` (its visible values only).
-__global__ __launch_bounds__(MDB_WAVE) void k_mv_range_partials(const MvSeg *__restrict__ segs, uint64_t n_slots,
-                                                                const float *__restrict__ values,
-                                                                RangePartial *__restrict__ partials,
-                                                                DeferredResult *__restrict__ result) {
-    const uint32_t slot = blockIdx.x;
-    const uint32_t lane = threadIdx.x;
-    const MvSeg seg = segs[slot];
-    RangePartial mine;
-    mine.clear();
-    if (!seg.done) {
-        // The parallel decoder gave this stream up: decode it here, one lane.
-        if (lane != 0) return;
-        uint32_t error = 0;
-        decode_macaque_v(reinterpret_cast<const uint8_t *>(seg.words) + seg.bias_bits / 8, seg.total_bits / 8,
-                         seg.visible_end, false, 0, &error, [&](uint32_t k, uint32_t bits) {
-                             if (k >= seg.first) mine.point(__uint_as_float(bits));
-                         });
-        if (error) atomicOr(&result->error, error);
-        partials[slot] = mine;
-        return;
-    }
-    const float *__restrict__ v = values + seg.out_offset;
-    const uint32_t n = seg.visible_end - seg.first;
-    for (uint32_t k = lane; k < n; k += MDB_WAVE) mine.point(v[k]);
-#pragma unroll
-    for (int delta = MDB_WAVE / 2; delta > 0; delta >>= 1) mine.merge(shfl_down_partial(mine, delta));
-    if (lane == 0) partials[slot] = mine;
-}
-
-// One lane per stream, out of the LDS ring (too many streams for the parallel decoder to pay off).
-__global__ __launch_bounds__(SERIAL_THREADS) void k_mv_serial_range(const MvSeg *__restrict__ segs, uint64_t n_slots,
-                                                                   RangePartial *__restrict__ partials,
-                                                                   DeferredResult *__restrict__ result) {
-    __shared__ uint32_t ring[SERIAL_RING_WORDS][MDB_WAVE];
-    const int lane = threadIdx.x;
-    const uint64_t slot = (uint64_t)blockIdx.x * SERIAL_THREADS + lane;
-    bool active = slot < n_slots;
-    RingBitReader reader;
-    reader.begin(nullptr, 0);
-    MacaqueStream stream;
-    stream.remaining = 0; stream.position = 0; stream.last = 0;
-    stream.leading = 255; stream.trailing = 0; stream.first_is_raw = true; stream.fresh = true;
-    uint32_t first = 0;
-    if (active) {
-        const MvSeg seg = segs[slot];
-        reader.begin(reinterpret_cast<const uint8_t *>(seg.words) + seg.bias_bits / 8, seg.total_bits / 8);
-        stream.remaining = seg.visible_end; // the format has no random access: from the beginning
-        first = seg.first;
-        active = seg.visible_end > 0 && seg.total_bits > 0;
-    }
-    RangePartial mine;
-    mine.clear();
-    uint32_t error = 0;
-    while (__any(active)) {
-        if (__any(active && reader.hungry())) ring_top_up(reader, ring, lane, active);
-        if (active) {
-            bool malformed;
-            const float value = __uint_as_float(ring_decode_value(reader, stream, ring, lane, &malformed));
-            if (stream.position >= first) mine.point(value);
-            stream.position += 1;
-            stream.remaining -= 1;
-            if (malformed || reader.overrun()) error |= ERR_BITSTREAM;
-            if (malformed || reader.overrun() || stream.remaining == 0) active = false;
-        }
-    }
-    if (slot < n_slots) partials[slot] = mine;
-    if (error) atomicOr(&result->error, error);
-}
-
-__global__ __launch_bounds__(MV_FINISH_THREADS) void k_mv_range_finish(const RangePartial *__restrict__ partials,
-                                                                       uint64_t n_slots,
-                                                                       DeferredResult *__restrict__ result) {
-    __shared__ RangePartial lds[MV_FINISH_THREADS];
-    RangePartial mine;
-    mine.clear();
-    for (uint64_t slot = threadIdx.x; slot < n_slots; slot += MV_FINISH_THREADS) mine.merge(partials[slot]);
-    lds[threadIdx.x] = mine;
-    __syncthreads();
-    for (int width = MV_FINISH_THREADS / 2; width > 0; width >>= 1) {
-        if ((int)threadIdx.x < width) {
-            RangePartial a = lds[threadIdx.x];
-            a.merge(lds[threadIdx.x + width]);
-            lds[threadIdx.x] = a;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        result->sum = lds[0].sum;
-        result->count = lds[0].count;
-        result->min = lds[0].min;
-        result->max = lds[0].max;
-    }
-}
-
-// Aggregates under a time range over a batch with cursors into its MacaqueV streams (a resident batch's sidecar, or
-// what the call's host threads left): one lane per piece of 64 values, as k_grid_mv_pieces - but only the pieces that
-// reach into the range are decoded, and only as far as it goes; what the points inside it contribute (GridExec +
-// filter + aggregate: f64 sum of the f32 values, count, extremes) is reduced per wave. Taken are the MacaqueV
-// segments with regular timestamps, no residuals and pieces in the index - the ones k_agg_range leaves out by the
-// same test (mv_range_by_pieces) - and the residual tails of PMC-Mean and Swing segments with regular timestamps
-// (mv_range_tail_by_pieces; a resident batch's index has their cursors: in k_agg_range a tenth of the lanes of a
-// wave would each decode one while the others wait).
-__global__ __launch_bounds__(MDB_WAVE) void k_agg_mv_range(DevSegments s, TimeRange range, const MvCursor *__restrict__ cursors,
-                                                           unsigned long long n_pieces, RangePartial *__restrict__ partials) {
-    __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
-    const int lane = threadIdx.x;
-    const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
-    const uint8_t *values_first = first_buffer(s.values), *residuals_first = first_buffer(s.residuals); // (see view_data())
-    RangePartial mine;
-    mine.clear();
-    uint32_t to_decode = 0, to_skip = 0;
-    PieceReader reader;
-    PieceState state;
-    reader.idle(cursors);
-    state.last = 0; state.trailing = 0; state.window_bits = 0; state.raw = false;
-    if (piece < n_pieces) {
-        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-        const uint32_t i = c0.z, point_index = c0.w, n_values = c1.x, window = c1.y;
-        // (a segment with irregular timestamps is not this kernel's, mv_range_by_pieces: it is left before the analysis,
-        // which would walk its timestamp stream to count its points - 0.9 ms per 10^9 points of such series)
-        const uint4 ts_view = s.timestamps.views[i];
-        const bool irregular = (int32_t)ts_view.x > 0 && (view_inline_byte(ts_view, 0) & 0x80u) != 0;
-        if (!irregular && !(s.end_time[i] < range.lo || s.start_time[i] > range.hi)) {
-            SegInfo info = analyse_segment(s, i);
-            const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
-            if (residual ? mv_range_tail_by_pieces(s, i, info) : mv_range_by_pieces(s, i, info)) {
-                // (a tail is XOR-seeded with the model's last RECONSTRUCTED value, models/mod.rs:241-249: what grid() sees)
-                const uint32_t seed = residual ? __float_as_uint(info.desc.value) : 0u;
-                apply_time_range(s, i, info, range);
-                const uint32_t from = max(point_index, info.desc.first);
-                const uint32_t upto = min(point_index + n_values, info.desc.first + info.desc.n_visible);
-                if (info.desc.n_visible > 0 && from < upto) {
-                    to_decode = upto - point_index;
-                    to_skip = from - point_index;
-                    const DevCol &column = residual ? s.residuals : s.values;
-                    const uint4 view = column.views[i];
-                    reader.open(view_data(column, i, view, residual ? residuals_first : values_first),
-                                residual ? (uint64_t)view.x - 1u : (uint64_t)view.x, c0.x);
-                    state.last = seed ^ c0.y;
-                    const uint32_t leading = window & 255u, trailing = (window >> 8) & 255u;
-                    state.trailing = trailing & 31u;
-                    state.window_bits = leading + trailing <= 32u ? 32u - leading - trailing : 0u;
-                    state.raw = (window & MV_WINDOW_RAW) != 0;
-                }
-            }
-        }
-    }
-    if (!__any(to_decode > 0)) { // (no piece of the wave reaches into the range)
-        if (lane == 0) partials[blockIdx.x] = mine;
-        return;
-    }
-    reader.begin();
-    reader.top_up(ring, lane);
-    reader.top_up(ring, lane);
-    reader.start(ring, lane);
-    // (every lane decodes in every step - straight-line code -, the values wanted are taken)
-    for (uint32_t k = 0, most = wave_max_u32(to_decode); k < most; k += 2) {
-        if (__any(reader.hungry())) reader.top_up(ring, lane);
-        const uint32_t even = piece_decode_value(reader, state, ring, lane);
-        const uint32_t odd = piece_decode_value(reader, state, ring, lane);
-        if (k >= to_skip && k < to_decode) mine.point(__uint_as_float(even));
-        if (k + 1 >= to_skip && k + 1 < to_decode) mine.point(__uint_as_float(odd));
-    }
-#pragma unroll
-    for (int delta = MDB_WAVE / 2; delta > 0; delta >>= 1) mine.merge(shfl_down_partial(mine, delta));
-    if (lane == 0) partials[blockIdx.x] = mine;
-}
-
-// ---- date_bin buckets over the pieces of MacaqueV streams (mdb_buckets.hip) ------------------------------------
-// The streams bucket_values_by_pieces / bucket_tail_by_pieces take (regular timestamps: point k at start + k delta)
-// are aggregated like k_agg_mv_range does under a time range - one lane per piece of 64 values, every lane decoding
-// in every step - but each lane flushes a partial at every bucket edge: ENTRIES {key, partial}, one per bucket its
-// visible values reach (empty ones included), at offsets a count per piece and a scan have given. Entries of one
-// stream follow each other in key order; mdb_buckets.hip reduces and folds them like its (segment, bucket) pairs.
-
-// The visible values [from, upto) of the piece (segment-level indices) and the buckets [b_first, b_last] they reach;
-// false: the piece is not taken or holds no visible value.
-__device__ __forceinline__ bool bucket_piece_span(const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
-                                                  const uint4 &c0, const uint4 &c1, SegInfo *info_out, uint32_t *from,
-                                                  uint32_t *upto, uint64_t *b_first, uint64_t *b_last) {
-    const uint32_t i = c0.z, point_index = c0.w, n_values = c1.x, window = c1.y;
-    const uint4 ts_view = s.timestamps.views[i];
-    if ((int32_t)ts_view.x > 0 && (view_inline_byte(ts_view, 0) & 0x80u) != 0) return false; // (irregular: not taken)
-    uint64_t unused = 0;
-    if (bucket_span(s.start_time[i], s.end_time[i], r, &unused) == 0) return false;
-    const SegInfo info = analyse_segment(s, i);
-    const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
-    if (!(residual ? bucket_tail_by_pieces(s, i, info, piece_base) : bucket_values_by_pieces(s, i, info, piece_base)))
-        return false;
-    const int64_t lo = r.t_lo > r.origin ? r.t_lo : r.origin;
-    const int64_t last = buckets_last_time(r);
-    const int64_t hi = r.t_hi < last ? r.t_hi : last;
-    uint32_t k_lo = 0, k_hi = 0;
-    if (lo > hi || !regular_index_interval(info.desc.start, info.desc.delta, info.desc.n_total, lo, hi, &k_lo, &k_hi))
-        return false;
-    *from = max(k_lo, point_index);
-    *upto = min(k_hi + 1, point_index + n_values);
-    if (*from >= *upto) return false;
-    const SegDesc &d = info.desc;
-    const uint64_t width = (uint64_t)r.width;
-    *b_first = ((uint64_t)(d.start + (int64_t)((uint64_t)*from * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
-    *b_last = ((uint64_t)(d.start + (int64_t)((uint64_t)(*upto - 1) * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
-    *info_out = info;
-    return true;
-}
-
-__global__ __launch_bounds__(256) void k_agg_bucket_piece_count(DevSegments s, BucketRequest r,
-                                                                 const unsigned long long *__restrict__ piece_base,
-                                                                 const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
-                                                                 unsigned long long *__restrict__ counts) {
-    const unsigned long long piece = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
-    if (piece >= n_pieces) return;
-    const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-    const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-    SegInfo info;
-    uint32_t from, upto;
-    uint64_t b_first, b_last;
-    counts[piece] = bucket_piece_span(s, r, piece_base, c0, c1, &info, &from, &upto, &b_first, &b_last)
-                        ? b_last - b_first + 1 : 0;
-}
-
-// Writes the entries [e0, e1) of the call (entry e at e - e0). Pred (AllValues, or the ValueKeys of
-// mdb_agg_buckets_filter*) says which decoded values are accumulated: the entries, and the decode, stay the same.
-template <typename Pred>
-__global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, BucketRequest r, const uint32_t *__restrict__ groups,
-                                                                const unsigned long long *__restrict__ piece_base,
-                                                                const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
-                                                                const unsigned long long *__restrict__ offsets,
-                                                                unsigned long long e0, unsigned long long e1,
-                                                                unsigned long long *__restrict__ keys,
-                                                                BucketPartial *__restrict__ out, Pred pred) {
-    static_assert(!Pred::by_row, "the buckets select by value: rows are not threaded through them");
-    __shared__ uint32_t ring[PIECE_RING_ROWS][MDB_WAVE];
-    const int lane = threadIdx.x;
-    const unsigned long long piece = (unsigned long long)blockIdx.x * MDB_WAVE + lane;
-    const uint8_t *values_first = first_buffer(s.values), *residuals_first = first_buffer(s.residuals); // (see view_data())
-    uint32_t to_decode = 0, to_skip = 0, point_index = 0;
-    uint64_t b_first = 0, b_last = 0, base = 0, row = 0;
-    int64_t start = 0, delta = 0;
-    PieceReader reader;
-    PieceState state;
-    reader.idle(cursors);
-    state.last = 0; state.trailing = 0; state.window_bits = 0; state.raw = false;
-    if (piece < n_pieces && offsets[piece + 1] > e0 && offsets[piece] < e1) {
-        const uint4 c0 = load_global(reinterpret_cast<const uint4 *>(cursors + piece));
-        const uint4 c1 = load_global(reinterpret_cast<const uint4 *>(cursors + piece) + 1);
-        SegInfo info;
-        uint32_t from, upto;
-        if (bucket_piece_span(s, r, piece_base, c0, c1, &info, &from, &upto, &b_first, &b_last)) {
-            const uint32_t i = c0.z, window = c1.y;
-            point_index = c0.w;
-            const bool residual = (window & MV_WINDOW_RESIDUAL) != 0;
-            // (a tail is XOR-seeded with the model's last RECONSTRUCTED value, models/mod.rs:241-249: what grid() sees)
-            const uint32_t seed = residual ? __float_as_uint(info.desc.value) : 0u;
-            to_decode = upto - point_index;
-            to_skip = from - point_index;
-            start = info.desc.start;
-            delta = info.desc.delta;
-            base = offsets[piece];
-            row = (uint64_t)(groups ? groups[i] : 0u) * r.n_buckets;
-            const DevCol &column = residual ? s.residuals : s.values;
-            const uint4 view = column.views[i];
-            reader.open(view_data(column, i, view, residual ? residuals_first : values_first),
-                        residual ? (uint64_t)view.x - 1u : (uint64_t)view.x, c0.x);
-            state.last = seed ^ c0.y;
-            const uint32_t leading = window & 255u, trailing = (window >> 8) & 255u;
-            state.trailing = trailing & 31u;
-            state.window_bits = leading + trailing <= 32u ? 32u - leading - trailing : 0u;
-            state.raw = (window & MV_WINDOW_RAW) != 0;
-        }
-    }
-    if (!__any(to_decode > 0)) return;
-    RangePartial acc;
-    acc.clear();
-    uint64_t bucket = b_first;
-    auto flush = [&]() {
-        const uint64_t e = base + (bucket - b_first);
-        if (e >= e0 && e < e1) {
-            keys[e - e0] = row + bucket;
-            out[e - e0] = BucketPartial{acc.sum, acc.count, acc.min, acc.max};
-        }
-        acc.clear();
-        bucket++;
-    };
-    auto take = [&](uint32_t k, uint32_t bits) {
-        if (k < to_skip || k >= to_decode) return;
-        const int64_t t = start + (int64_t)((uint64_t)(point_index + k) * (uint64_t)delta);
-        const uint64_t b = ((uint64_t)t - (uint64_t)r.origin) / (uint64_t)r.width;
-        while (bucket < b) flush();
-        if (pred.counts(__uint_as_float(bits), 0)) acc.point(__uint_as_float(bits)); // (by value: Pred::by_row is false)
-    };
-    reader.begin();
-    reader.top_up(ring, lane);
-    reader.top_up(ring, lane);
-    reader.start(ring, lane);
-    for (uint32_t k = 0, most = wave_max_u32(to_decode); k < most; k += 2) {
-        if (__any(reader.hungry())) reader.top_up(ring, lane);
-        const uint32_t even = piece_decode_value(reader, state, ring, lane);
-        const uint32_t odd = piece_decode_value(reader, state, ring, lane);
-        take(k, even);
-        take(k + 1, odd);
-    }
-    if (to_decode > 0) flush(); // (bucket == b_last)
-}
-
-struct BucketPieceCountOf {
-    const unsigned long long *counts;
-    __device__ uint64_t operator()(uint64_t k) const { return counts[k]; }
-};
-
-int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
-                        const MvIndex &index, const unsigned long long **offsets_out, unsigned long long *total) {
-    *total = 0;
-    const uint64_t n = index.n_pieces;
-    void *p = nullptr;
-    const uint64_t counts_bytes = align_up(n * 8, 256), offsets_bytes = align_up((n + 1) * 8, 256);
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PIECES, counts_bytes + offsets_bytes + scan_block_sums_bytes(n) + 256, &p))
-        return 1;
-    unsigned long long *counts = static_cast<unsigned long long *>(p);
-    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes);
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(static_cast<char *>(p) + counts_bytes + offsets_bytes);
-    {
-        LaunchTimer timer(ctx, "k_agg_bucket_piece_count");
-        hipLaunchKernelGGL(k_agg_bucket_piece_count, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, ctx->stream, s, r,
-                           piece_base, static_cast<const MvCursor *>(index.cursors), (unsigned long long)n, counts);
-    }
-    if (device_exclusive_scan(ctx, BucketPieceCountOf{counts}, n, offsets, block_sums, "k_agg_bucket_piece_count")) return 1;
-    MDB_HIP_CHECK(hipMemcpyAsync(total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    *offsets_out = offsets;
-    return 0;
-}
-
-int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const uint32_t *groups,
-                          const unsigned long long *piece_base, const MvIndex &index, const unsigned long long *offsets,
-                          unsigned long long e0, unsigned long long e1, unsigned long long *keys, BucketPartial *out,
-                          const ValueKeys *filter) {
-    const uint64_t n = index.n_pieces;
-    const dim3 blocks((uint32_t)((n + MDB_WAVE - 1) / MDB_WAVE));
-    const MvCursor *cursors = static_cast<const MvCursor *>(index.cursors);
-    if (filter) {
-        LaunchTimer timer(ctx, "k_agg_bucket_pieces_filter");
-        hipLaunchKernelGGL(k_agg_bucket_pieces<ValueKeys>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
-                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, *filter);
-    } else {
-        LaunchTimer timer(ctx, "k_agg_bucket_pieces");
-        hipLaunchKernelGGL(k_agg_bucket_pieces<AllValues>, blocks, dim3(MDB_WAVE), 0, ctx->stream, s, r, groups,
-                           piece_base, cursors, (unsigned long long)n, offsets, e0, e1, keys, out, AllValues());
-    }
-    return 0;
-}
-
-// One workgroup, fixed order (strided partial sums, then a fixed tree): the result does not depend
-// on how the work was scheduled.
-__global__ __launch_bounds__(MV_FINISH_THREADS) void k_mv_sums_finish(const float *__restrict__ sums, uint64_t n_slots,
-                                                                      DeferredResult *__restrict__ result) {
-    __shared__ double partial[MV_FINISH_THREADS];
-    double sum = 0.0;
-    for (uint64_t slot = threadIdx.x; slot < n_slots; slot += MV_FINISH_THREADS) sum += (double)sums[slot];
-    partial[threadIdx.x] = sum;
-    __syncthreads();
-    for (int width = MV_FINISH_THREADS / 2; width > 0; width >>= 1) {
-        if ((int)threadIdx.x < width) partial[threadIdx.x] += partial[threadIdx.x + width];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) result->sum = partial[0];
-}
-
 uint32_t macaque_parallel_min_values(bool *forced) {
     *forced = option_text("MDB_GRID_MV_MIN_VALUES") != nullptr;
     return mv_min_values_setting();
 }
 
-// The long MacaqueV streams k_agg_segments / k_agg_range left aside (mv_deferred_values; the caller has
-// counted them: n_streams streams, n_values values to decode into scratch memory at most, n_bytes
-// bytes). Without a range: each stream added up in f32 in stream order, the streams in f64
-// (totals->sum). With one: SUM (f64), COUNT, MIN and MAX of the values inside it. *handled stays
-// false only when the counts are beyond what the scan item can carry.
-int macaque_deferred(mdb_ctx *ctx, const DevSegments &s, TimeRange range, uint32_t min_values, bool forced,
-                     uint64_t n_streams, uint64_t n_values, uint64_t n_bytes, bool *handled,
-                     DeferredTotals *totals, const unsigned long long *by_pieces) {
-    *handled = false;
-    if (n_streams == 0 || n_values >= DEFERRED_ONE) return 0;
-    // Few enough streams for the parallel decoder (the gate of mv_pipeline)? Then their values go to
-    // scratch memory first; otherwise a lane per stream decodes and accumulates in one go.
-    const bool parallel = n_bytes * 8 / MV_PIECE_BITS + n_streams + 1 <= MV_MAX_PIECES || forced;
-    const uint64_t scan_bytes = align_up((s.n + 1) * 8, 256);
-    const uint64_t block_sums_bytes = align_up(scan_block_sums_bytes(s.n), 256);
-    const uint64_t values_bytes = parallel ? align_up(n_values * 4, 256) : 256;
-    const uint64_t per_stream_bytes = align_up(n_streams * sizeof(RangePartial), 256); // or one float each
-    void *p = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_AGG_MV, scan_bytes + block_sums_bytes + values_bytes + per_stream_bytes + 256, &p))
-        return 1;
-    uint8_t *at = static_cast<uint8_t *>(p);
-    unsigned long long *scan = reinterpret_cast<unsigned long long *>(at);
-    at += scan_bytes;
-    unsigned long long *block_sums = reinterpret_cast<unsigned long long *>(at);
-    at += block_sums_bytes;
-    float *values = reinterpret_cast<float *>(at);
-    at += values_bytes;
-    float *sums = reinterpret_cast<float *>(at);
-    RangePartial *partials = reinterpret_cast<RangePartial *>(at);
-    at += per_stream_bytes;
-    DeferredResult *result = reinterpret_cast<DeferredResult *>(at);
-    MDB_HIP_CHECK(hipMemsetAsync(result, 0, sizeof(DeferredResult), ctx->stream));
-    if (device_exclusive_scan(ctx, DeferredItem{s, min_values, range, by_pieces}, s.n, scan, block_sums, "k_mv_deferred_scan"))
-        return 1;
-    auto select = [&](MvSeg *segs) {
-        LaunchTimer timer(ctx, "k_mv_select");
-        hipLaunchKernelGGL(k_mv_select_scanned, dim3((uint32_t)((s.n + 255) / 256)), dim3(256), 0, ctx->stream, s,
-                           range, scan, min_values, segs);
-    };
-    MvSeg *segs = nullptr;
-    if (parallel && mv_pipeline(ctx, n_streams, n_bytes, forced, select, values, &result->error, &segs)) return 1;
-    const bool decoded = segs != nullptr;
-    if (!decoded) {
-        void *q = nullptr;
-        if (scratch_reserve(ctx, SCRATCH_MV, n_streams * sizeof(MvSeg), &q)) return 1;
-        segs = static_cast<MvSeg *>(q);
-        select(segs);
-    }
-    const uint32_t lane_blocks = (uint32_t)((n_streams + SERIAL_THREADS - 1) / SERIAL_THREADS);
-    if (range.enabled) {
-        if (decoded) {
-            LaunchTimer timer(ctx, "k_mv_range_partials");
-            hipLaunchKernelGGL(k_mv_range_partials, dim3((uint32_t)n_streams), dim3(MDB_WAVE), 0, ctx->stream, segs,
-                               n_streams, values, partials, result);
-        } else {
-            LaunchTimer timer(ctx, "k_mv_serial_range");
-            hipLaunchKernelGGL(k_mv_serial_range, dim3(lane_blocks), dim3(SERIAL_THREADS), 0, ctx->stream, segs,
-                               n_streams, partials, result);
-        }
-        LaunchTimer timer(ctx, "k_mv_range_finish");
-        hipLaunchKernelGGL(k_mv_range_finish, dim3(1), dim3(MV_FINISH_THREADS), 0, ctx->stream, partials, n_streams,
-                           result);
-    } else {
-        if (decoded) {
-            LaunchTimer timer(ctx, "k_mv_sums");
-            hipLaunchKernelGGL(k_mv_sums, dim3((uint32_t)n_streams), dim3(MDB_WAVE), 0, ctx->stream, segs, n_streams,
-                               values, sums, result);
-        } else {
-            LaunchTimer timer(ctx, "k_mv_serial_sums");
-            hipLaunchKernelGGL(k_mv_serial_sums, dim3(lane_blocks), dim3(SERIAL_THREADS), 0, ctx->stream, segs,
-                               n_streams, sums, result);
-        }
-        LaunchTimer timer(ctx, "k_mv_sums_finish");
-        hipLaunchKernelGGL(k_mv_sums_finish, dim3(1), dim3(MV_FINISH_THREADS), 0, ctx->stream, sums, n_streams, result);
-    }
-    DeferredResult host;
-    MDB_HIP_CHECK(hipMemcpyAsync(&host, result, sizeof(DeferredResult), hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    if (host.error) return fail(describe_error(host.error));
-    *handled = true;
-    totals->sum = host.sum;
-    totals->count = host.count;
-    totals->min = host.min;
-    totals->max = host.max;
-    return 0;
-}
-
 // For agg_run under a time range: the batch's cursor index if it has a usable one (*piece_base stays nullptr
-// otherwise) - call it before the aggregates lay out their scratch, a resident batch's index is built here - ...
+// otherwise) - call it before the aggregates lay out their scratch, a resident batch's index is built here.
+// (mv_index_range_totals, mdb_agg_mv.hip, then says what the indexed segments' points inside the range add up to.)
 int mv_index_for_range(mdb_ctx *ctx, const mdb_segments *in, std::shared_ptr<MvIndex> *index, const unsigned long long **piece_base) {
     *piece_base = nullptr;
     if (mv_index_prepare(ctx, in, index)) return 1;
@@ -4458,33 +2967,6 @@ int mv_index_for_range(mdb_ctx *ctx, const mdb_segments *in, std::shared_ptr<MvI
         return 0;
     }
     *piece_base = static_cast<const unsigned long long *>((*index)->piece_base);
-    return 0;
-}
-// ... and what the indexed MacaqueV segments' points inside the range add up to (k_agg_mv_range).
-int mv_index_range_totals(mdb_ctx *ctx, const DevSegments &s, TimeRange range, const MvIndex &index, DeferredTotals *totals) {
-    const uint32_t n_blocks = (uint32_t)((index.n_pieces + MDB_WAVE - 1) / MDB_WAVE);
-    void *p = nullptr;
-    if (scratch_reserve(ctx, SCRATCH_AGG_MV, (uint64_t)n_blocks * sizeof(RangePartial) + 256, &p)) return 1;
-    RangePartial *partials = static_cast<RangePartial *>(p);
-    DeferredResult *result = reinterpret_cast<DeferredResult *>(reinterpret_cast<uint8_t *>(p) + align_up((uint64_t)n_blocks * sizeof(RangePartial), 256));
-    MDB_HIP_CHECK(hipMemsetAsync(result, 0, sizeof(DeferredResult), ctx->stream));
-    {
-        LaunchTimer timer(ctx, "k_agg_mv_range");
-        hipLaunchKernelGGL(k_agg_mv_range, dim3(n_blocks), dim3(MDB_WAVE), 0, ctx->stream, s, range,
-                           static_cast<const MvCursor *>(index.cursors), index.n_pieces, partials);
-    }
-    {
-        LaunchTimer timer(ctx, "k_mv_range_finish");
-        hipLaunchKernelGGL(k_mv_range_finish, dim3(1), dim3(MV_FINISH_THREADS), 0, ctx->stream, partials, (uint64_t)n_blocks, result);
-    }
-    DeferredResult host;
-    MDB_HIP_CHECK(hipMemcpyAsync(&host, result, sizeof(DeferredResult), hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    totals->sum = host.sum;
-    totals->count = host.count;
-    totals->min = host.min;
-    totals->max = host.max;
     return 0;
 }
 

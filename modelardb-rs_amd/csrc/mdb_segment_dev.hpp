@@ -807,7 +807,7 @@ __device__ __forceinline__ bool mv_qualifies_for_sum(const SegInfo &info, uint32
     return mv_qualifies(info, values_bytes, min_values) && length == info.desc.n_model;
 }
 
-// Aggregates leave long MacaqueV streams to the decoders of mdb_grid.hip (macaque_deferred_sum): how
+// Aggregates leave long MacaqueV streams to the decoders of mdb_agg_mv.hip (macaque_deferred): how
 // many values of segment i that would be - none if it does not qualify. `info` is what
 // analyse_segment() said about it. With a time range: the values up to the last one inside it
 // (regular timestamps only; what is summed there is what grid() would produce, so grid()'s length
@@ -822,7 +822,7 @@ __device__ __forceinline__ uint32_t mv_deferred_values(const DevSegments &s, uin
 }
 
 // Under a time range, with cursors into the batch's MacaqueV streams: is segment i (analysed: `info`) aggregated piece
-// by piece (k_agg_mv_range, mdb_grid.hip) rather than by k_agg_range's lane? Evaluated identically by both; the
+// by piece (k_agg_mv_range, mdb_agg_mv.hip) rather than by k_agg_range's lane? Evaluated identically by both; the
 // caller adds that the segment has pieces in the index.
 __device__ __forceinline__ bool mv_range_by_pieces(const DevSegments &s, uint64_t i, const SegInfo &info) {
     const SegDesc &d = info.desc;

@@ -1,5 +1,5 @@
 // Runs the parallel MacaqueV decoder's kernels on ONE stream read from a file and prints what every
-// stage produced (development tool for mdb_macaque_parallel.hpp).
+// stage produced (development tool for mdb_macaque_parallel.hpp; the kernels are mdb_mv_parallel.hip's, included whole).
 // usage: mv_debug stream.bin n_values
 #define MDB_MV_DEBUG 1
 #include <hip/hip_runtime.h>
@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 #include "../../modelardb-rs_amd/csrc/mdb_common.hpp"
-#include "../../modelardb-rs_amd/csrc/mdb_macaque_parallel.hpp"
+#include "../../modelardb-rs_amd/csrc/mdb_mv_parallel.hip"
 namespace mdb { thread_local std::string g_last_error; }
 using namespace mdb;
 #define CHECK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
@@ -56,7 +56,7 @@ int main(int argc, char **argv) {
         hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
         CHECK(hipDeviceSynchronize());
         hipEventRecord(e0);
-        hipLaunchKernelGGL(k_mv_chains, dim3((P * MV_CHAINS + 63) / 64), dim3(64), 0, 0, segs, piece_base, 1ull, round, guesses, tried, pending, heads, chains);
+        hipLaunchKernelGGL(k_mv_chains<MV_STAGE_WORDS>, dim3((P * MV_CHAINS + 63) / 64), dim3(64), 0, 0, segs, piece_base, 1ull, round, guesses, tried, pending, heads, chains);
         hipEventRecord(e1);
         CHECK(hipDeviceSynchronize());
         float ms = 0; hipEventElapsedTime(&ms, e0, e1);
@@ -76,7 +76,7 @@ int main(int argc, char **argv) {
     }
     hipLaunchKernelGGL(k_mv_links, dim3((P * MV_CHAINS + 63) / 64), dim3(64), 0, 0, segs, piece_base, 1ull, heads, chains, links);
     hipLaunchKernelGGL(k_mv_walk, dim3(1), dim3(64), 0, 0, segs, piece_base, chains, links, starts);
-    hipLaunchKernelGGL(k_mv_decode, dim3(blocks), dim3(64), 0, 0, segs, piece_base, 1ull, starts, out, error);
+    hipLaunchKernelGGL(k_mv_decode<MV_STAGE_WORDS>, dim3(blocks), dim3(64), 0, 0, segs, piece_base, 1ull, starts, out, error);
     CHECK(hipDeviceSynchronize());
     std::vector<MvLink> host_links((size_t)P * MV_CHAINS);
     std::vector<MvStart> host_starts(P);

@@ -24,7 +24,7 @@ SUM_TOLERANCE = 1e-5  # 0.001 %
                 ids=["mv-default", "mv-off", "mv-from-8-values", "timestamps-every-lane-for-itself",
                      "mv-cursors-by-host-threads"])
 def macaque_decoder(request, monkeypatch):
-    """SUM leaves long MacaqueV streams to the parallel decoder (macaque_deferred_sum in mdb_grid.hip):
+    """SUM leaves long MacaqueV streams to the parallel decoder (macaque_deferred in mdb_agg_mv.hip):
     every test runs with its default threshold, with it switched off and with every stream of at
     least 8 values going that way. len() and swing::sum of segments with irregular timestamps come from the
     wave-synchronous walk of their streams (k_grid_ts_count<SUMS>), or - the last mode - from every lane
