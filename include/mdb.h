@@ -431,6 +431,44 @@ int mdb_hist_cell_of(const float *edges, uint32_t n_edges, float value, uint32_t
  * *fraction = p - floor(p). Errors: n_points == 0, q outside [0, 1] or NaN, a NULL output. */
 int mdb_quantile_positions(double q, uint64_t n_points, uint64_t *rank_lo, uint64_t *rank_hi, double *fraction);
 
+/* Extension: M4 downsampling - per bucket of date_bin(width, ts, origin) and group the first, last, lowest and highest
+ * data point WITH their timestamps: what a plotting front end asks a time-series store for per pixel column. The
+ * reference answers it with GridExec -> AggregateExec(first_value / last_value(field ORDER BY ts), min, max) GROUP BY
+ * the date_bin, and a join of the result back onto the points for the timestamps of the minimum and maximum: every
+ * point is rebuilt first. Here the cells are computed on the segments and no point is materialised.
+ *   request: mdb_bucket_request, unchanged; which_mask must be 0. inout: row-major [n_groups][n_buckets] cells
+ *     (mdb_m4_cell, mdb_format.h); a fresh cell is all-zero bytes. group_of_segment as for mdb_agg_buckets.
+ *   Which points: exactly those mdb_agg_buckets counts for the same request - bucket floor((t - origin) / width) in
+ *     [0, n_buckets) and t in [t_lo, t_hi]; a point of segment row i goes to group group_of_segment[i].
+ *   Which of them, with key(v) the totalOrder key of mdb_value_filter:
+ *     first = the point with the smallest (t, key(v)), compared lexicographically; last = the largest (t, key(v));
+ *     min = the smallest (key(v), t); max = the largest key(v) and, among those, the smallest t; count = how many.
+ *     In a group that holds one series timestamps are unique: first / last are first_value / last_value(field ORDER
+ *     BY ts), min / max the extreme values at their earliest occurrence.
+ *   Each rule is commutative and associative, so a cell depends only on the SET of its points: not on the order of
+ *     the segments, on how a batch is cut into calls or list entries, on the slice size
+ *     (MDB_AGG_BUCKET_SLICE_PAIRS), on whether the keys had to be sorted, or on the shape of the reduction tree. The
+ *     host, dev and list forms agree bit for bit, and so do two runs; folding the halves of a batch into the same
+ *     cells, in either order, gives the bytes of the whole batch.
+ *   Merging: a call merges its batch into inout by the same rules (mdb_m4_merge_n is that rule on the host, cell by
+ *     cell: into[j] = into[j] + from[j]). A cell that receives no point keeps every byte it had.
+ *   Against mdb_agg_buckets: count equals its COUNT, always. In a cell without a NaN, v_min / v_max compare equal
+ *     (==) to its MIN / MAX. They differ with NaNs: that operator skips them (min_num / max_num), totalOrder places
+ *     them (-NaN below -inf, +NaN above +inf), so a cell with a NaN reports it as v_min or v_max. -0.0 is below +0.0.
+ *   Errors (mdb_last_error set, inout untouched): a NULL argument, which_mask != 0, and those of mdb_agg_buckets -
+ *     width <= 0, n_groups == 0, n_groups * n_buckets overflowing, a group id >= n_groups on any row, a malformed
+ *     segment among those the request reaches. An empty batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_m4_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                   const mdb_bucket_request *request, mdb_m4_cell *inout);
+/* All device pointers: the segments, group_of_segment and inout are in HBM. */
+int mdb_m4_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                       const mdb_bucket_request *request, mdb_m4_cell *inout);
+/* Several host batches (rows in the order of the list) folded as one batch, as mdb_agg_buckets_list does. */
+int mdb_m4_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                        uint32_t n_inputs, const mdb_bucket_request *request, mdb_m4_cell *inout);
+/* Host arithmetic, no context, no GPU: into[j] merged with from[j] for j < n. */
+int mdb_m4_merge_n(mdb_m4_cell *into, const mdb_m4_cell *from, uint64_t n);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -199,6 +199,15 @@ typedef struct mdb_hist_request {
     uint32_t reserved;     /* must be 0 */
 } mdb_hist_request;        /* 32 bytes */
 
+/* One cell of mdb_m4_buckets*: the first, last, lowest and highest point of a bucket and group, with their timestamps
+ * (the M4 aggregation: a line chart of the cell's points is redrawn exactly from these four). A fresh cell is all-zero
+ * bytes. count == 0: the cell is empty and no other member is read; all are written when its first point arrives. */
+typedef struct mdb_m4_cell {
+    int64_t count;
+    int64_t t_first, t_last, t_min, t_max;
+    float   v_first, v_last, v_min, v_max;
+} mdb_m4_cell;             /* 56 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -288,5 +297,14 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, n_edges) == 16);
 MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, n_groups) == 20);
 MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, flags) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_hist_request, reserved) == 28);
+MDB_LAYOUT_ASSERT(sizeof(mdb_m4_cell) == 56);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, t_first) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, t_last) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, t_min) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, t_max) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_first) == 40);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_last) == 44);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_min) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_max) == 52);
 
 #endif /* MDB_FORMAT_H */

@@ -182,6 +182,21 @@ class ValueFilterC(C.Structure):
     ]
 
 
+class M4CellC(C.Structure):
+    """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
+    _fields_ = [
+        ("count", C.c_int64),
+        ("t_first", C.c_int64),
+        ("t_last", C.c_int64),
+        ("t_min", C.c_int64),
+        ("t_max", C.c_int64),
+        ("v_first", C.c_float),
+        ("v_last", C.c_float),
+        ("v_min", C.c_float),
+        ("v_max", C.c_float),
+    ]
+
+
 class HistRequestC(C.Structure):
     """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
     _fields_ = [
@@ -263,6 +278,12 @@ _HIP_SYMBOLS = {
                                       C.c_void_p]),
     "mdb_agg_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
                                        C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_m4_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_m4_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                     C.c_void_p]),
+    "mdb_m4_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                      C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_m4_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_grid_count_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC),
                                             C.POINTER(C.c_uint64)]),
     "mdb_grid_batch_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_void_p,

@@ -139,6 +139,31 @@ def agg_merge_n(into, other):
     return into
 
 
+# mdb_m4_cell as a numpy record: the cells of mdb_m4_buckets*, row-major [n_groups][n_buckets].
+M4_CELL_DTYPE = np.dtype([("count", "<i8"), ("t_first", "<i8"), ("t_last", "<i8"), ("t_min", "<i8"), ("t_max", "<i8"),
+                          ("v_first", "<f4"), ("v_last", "<f4"), ("v_min", "<f4"), ("v_max", "<f4")])
+assert M4_CELL_DTYPE.itemsize == C.sizeof(_abi.M4CellC)
+
+
+def fresh_m4_cells(shape):
+    """Fresh (empty) M4 cells: all-zero bytes."""
+    return np.zeros(shape, dtype=M4_CELL_DTYPE)
+
+
+def m4_merge(into, from_):
+    """into[k] merged with from_[k] in place by the four rules of mdb_m4_buckets (mdb_m4_merge_n): two arrays of
+    M4_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != M4_CELL_DTYPE or from_.dtype != M4_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("m4_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("m4_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_m4_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -857,6 +882,60 @@ class Context:
             if dev_groups is not None:
                 self.dev_free(dev_groups)
         return states
+
+    # ---- M4 downsampling: first / last / min / max points per time bucket ----------------------------
+
+    @staticmethod
+    def _m4_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_m4_cells((n_groups, n_buckets))
+        if cells.dtype != M4_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of M4_CELL_DTYPE")
+        return cells
+
+    def m4_buckets(self, batch, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                   n_groups=None):
+        """The first, last, lowest and highest point (with timestamps) and the count per bucket of
+        date_bin(width, ts, origin) and group (mdb_m4_buckets): returns `cells` (or fresh ones), shape
+        (n_groups, n_buckets), merged in place. `groups` and n_groups as for agg_buckets."""
+        return self.m4_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups], t_lo,
+                                    t_hi, cells, n_groups)
+
+    def m4_buckets_list(self, batches, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                        n_groups=None):
+        """Several host batches merged as one (mdb_m4_buckets_list); `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._m4_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_m4_buckets_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                 cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def m4_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                       n_groups=None):
+        """mdb_m4_buckets_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._m4_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_m4_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                    None if dev_groups is None else C.c_void_p(dev_groups),
+                                                    C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, M4_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
 
     @staticmethod
     def _n_groups(n_groups, states, groups):

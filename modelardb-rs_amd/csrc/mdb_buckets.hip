@@ -26,8 +26,7 @@
 //                          entry per level up) and merges it into the cell - no two lanes write one cell, no float
 //                          atomics, the order of every addition fixed by the pair order: run-to-run deterministic.
 // Bytes (Swing on regular timestamps): ~70 B of metadata per segment read, 32 B per pair written and read back.
-#include "mdb_agg_dev.hpp"
-#include "mdb_mv_pieces.hpp"
+#include "mdb_buckets.hpp"
 #include "mdb_scan.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -38,13 +37,6 @@
 #include <vector>
 
 namespace mdb {
-
-constexpr int BUCKET_THREADS = 256;
-constexpr uint32_t BUCKET_TILE = 64;                    // entries per lane and level of the reduction tree
-constexpr int BUCKET_MAX_LEVELS = 12;                   // 64^11 > 2^64
-constexpr uint64_t BUCKET_SLICE_DEFAULT = 1ull << 24;   // pairs per slice: 512 MB of partials and keys
-constexpr uint64_t BUCKET_SLICE_MAX = 1ull << 31;       // (pair numbers of the sort path are 32-bit)
-constexpr uint32_t ERR_BUCKET_GROUP = 1u << 31;         // k_agg_bucket_span: a group id >= n_groups
 
 struct BucketTree { // level 0 is the slice's pairs (keys, partials, and the sort's pair numbers); 1.. are the tree's
     const unsigned long long *keys[BUCKET_MAX_LEVELS];
@@ -291,36 +283,7 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_fold(BucketTree t
 // visible values reach (empty ones included), at offsets a count per piece and a scan have given. Entries of one
 // stream follow each other in key order; buckets_run reduces and folds them like its (segment, bucket) pairs.
 
-// The visible values [from, upto) of the piece (segment-level indices) and the buckets [b_first, b_last] they reach;
-// false: the piece is not taken or holds no visible value.
-__device__ __forceinline__ bool bucket_piece_span(const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
-                                                  const PieceCursor &cursor, SegInfo *info_out, uint32_t *from,
-                                                  uint32_t *upto, uint64_t *b_first, uint64_t *b_last) {
-    const uint32_t i = cursor.segment(), point_index = cursor.point_index(), n_values = cursor.n_values();
-    const uint4 ts_view = s.timestamps.views[i];
-    if ((int32_t)ts_view.x > 0 && (view_inline_byte(ts_view, 0) & 0x80u) != 0) return false; // (irregular: not taken)
-    uint64_t unused = 0;
-    if (bucket_span(s.start_time[i], s.end_time[i], r, &unused) == 0) return false;
-    const SegInfo info = analyse_segment(s, i);
-    if (!(cursor.residual() ? bucket_tail_by_pieces(s, i, info, piece_base) : bucket_values_by_pieces(s, i, info, piece_base)))
-        return false;
-    const int64_t lo = r.t_lo > r.origin ? r.t_lo : r.origin;
-    const int64_t last = buckets_last_time(r);
-    const int64_t hi = r.t_hi < last ? r.t_hi : last;
-    uint32_t k_lo = 0, k_hi = 0;
-    if (lo > hi || !regular_index_interval(info.desc.start, info.desc.delta, info.desc.n_total, lo, hi, &k_lo, &k_hi))
-        return false;
-    *from = max(k_lo, point_index);
-    *upto = min(k_hi + 1, point_index + n_values);
-    if (*from >= *upto) return false;
-    const SegDesc &d = info.desc;
-    const uint64_t width = (uint64_t)r.width;
-    *b_first = ((uint64_t)(d.start + (int64_t)((uint64_t)*from * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
-    *b_last = ((uint64_t)(d.start + (int64_t)((uint64_t)(*upto - 1) * (uint64_t)d.delta)) - (uint64_t)r.origin) / width;
-    *info_out = info;
-    return true;
-}
-
+// (bucket_piece_span, the visible values of a piece and the buckets they reach: mdb_buckets.hpp)
 __global__ __launch_bounds__(256) void k_agg_bucket_piece_count(DevSegments s, BucketRequest r,
                                                                  const unsigned long long *__restrict__ piece_base,
                                                                  const MvCursor *__restrict__ cursors, unsigned long long n_pieces,
@@ -406,8 +369,8 @@ __global__ __launch_bounds__(MDB_WAVE) void k_agg_bucket_pieces(DevSegments s, B
 // The entries of the pieces taken above. bucket_pieces_count sizes them (offsets: per piece of the index, n_pieces + 1,
 // in scratch); bucket_pieces_entries writes the entries [e0, e1) to keys / out (at e - e0), with the values that pass
 // `filter` only (nullptr: every value; the entries are the same either way).
-static int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
-                               const MvIndex &index, const unsigned long long **offsets_out, unsigned long long *total) {
+int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest &r, const unsigned long long *piece_base,
+                        const MvIndex &index, const unsigned long long **offsets_out, unsigned long long *total) {
     *total = 0;
     const uint64_t n = index.n_pieces;
     void *p = nullptr;
@@ -449,9 +412,71 @@ static int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const Bucke
     return 0;
 }
 
-static uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + BUCKET_THREADS - 1) / BUCKET_THREADS); }
+// ---- the host steps mdb_m4.hip shares (mdb_buckets.hpp) --------------------------------------------------------
 
-static uint64_t slice_pairs_setting() {
+int bucket_span_pairs(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const uint32_t *groups,
+                      const BucketRequest &r, const unsigned long long **offsets_out, unsigned int **words_out,
+                      unsigned long long *total_out) {
+    const uint64_t n = in->n;
+    // Span: pair offsets and the read-back words (total pairs, error, unsorted).
+    void *p;
+    const uint64_t offsets_bytes = align_up((n + 1) * 8, 256), sums_bytes = align_up(scan_block_sums_bytes(n), 256);
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_SPAN, 2 * offsets_bytes + sums_bytes + 256, &p)) return 1;
+    Carver span(p);
+    unsigned long long *counts = span.take<unsigned long long>(n + 1);
+    unsigned long long *offsets = span.take<unsigned long long>(n + 1);
+    unsigned long long *block_sums = span.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
+    unsigned int *words = span.take<unsigned int>(2);
+    MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
+    {
+        LaunchTimer timer(ctx, "k_agg_bucket_span");
+        hipLaunchKernelGGL(k_agg_bucket_span, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, r,
+                           counts, words);
+    }
+    if (device_exclusive_scan(ctx, ItemsOf<unsigned long long>{counts}, n, offsets, block_sums, "k_agg_bucket_scan")) return 1;
+    unsigned long long total = 0;
+    unsigned int span_error = 0;
+    MDB_HIP_CHECK(hipMemcpyAsync(&total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipMemcpyAsync(&span_error, words, 4, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    if (span_error & ERR_BUCKET_GROUP) return fail("A group id is not below n_groups.");
+    *offsets_out = offsets;
+    *words_out = words;
+    *total_out = total;
+    return 0;
+}
+
+void bucket_keys_check(mdb_ctx *ctx, const unsigned long long *keys, uint64_t m, unsigned int *unsorted) {
+    if (m <= 1) return;
+    LaunchTimer timer(ctx, "k_agg_bucket_check");
+    hipLaunchKernelGGL(k_agg_bucket_check, dim3(blocks_for(m - 1)), dim3(BUCKET_THREADS), 0, ctx->stream, keys, m,
+                       unsorted);
+}
+
+int bucket_keys_sort(mdb_ctx *ctx, unsigned long long *keys, uint64_t m, unsigned int key_bits,
+                     const unsigned long long **sorted_out, const uint32_t **order_out) {
+    void *p;
+    const uint64_t keys_bytes = align_up(m * 8, 256), order_bytes = align_up(m * 4, 256);
+    size_t sort_bytes = 0;
+    MDB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys, static_cast<uint32_t *>(nullptr),
+                                            static_cast<uint32_t *>(nullptr), (size_t)m, 0u, key_bits, ctx->stream));
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_SORT, keys_bytes + 2 * order_bytes + sort_bytes, &p)) return 1;
+    Carver sort_scratch(p);
+    unsigned long long *sorted_keys = sort_scratch.take<unsigned long long>(m);
+    uint32_t *order_in = sort_scratch.take<uint32_t>(m);
+    uint32_t *order = sort_scratch.take<uint32_t>(m);
+    void *sort_storage = sort_scratch.at;
+    LaunchTimer timer(ctx, "k_agg_bucket_sort");
+    hipLaunchKernelGGL(k_agg_bucket_iota, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, order_in, m);
+    MDB_HIP_CHECK(rocprim::radix_sort_pairs(sort_storage, sort_bytes, keys, sorted_keys, order_in, order, (size_t)m,
+                                            0u, key_bits, ctx->stream));
+    *sorted_out = sorted_keys;
+    *order_out = order;
+    return 0;
+}
+
+uint64_t slice_pairs_setting() {
     if (const char *text = option_text("MDB_AGG_BUCKET_SLICE_PAIRS")) {
         const long long value = std::atoll(text);
         if (value >= 1) return std::min<uint64_t>((uint64_t)value, BUCKET_SLICE_MAX);
@@ -485,30 +510,12 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
         return fail("Too many (segment, bucket) pairs for one call: split the batch.");
     const DevSegments s = to_dev(in);
 
-    // Span: pair offsets and the read-back words (total pairs, error, unsorted).
-    void *p;
-    const uint64_t offsets_bytes = align_up((n + 1) * 8, 256), sums_bytes = align_up(scan_block_sums_bytes(n), 256);
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_SPAN, 2 * offsets_bytes + sums_bytes + 256, &p)) return 1;
-    Carver span(p);
-    unsigned long long *counts = span.take<unsigned long long>(n + 1);
-    unsigned long long *offsets = span.take<unsigned long long>(n + 1);
-    unsigned long long *block_sums = span.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
-    unsigned int *words = span.take<unsigned int>(2);
-    MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
-    {
-        LaunchTimer timer(ctx, "k_agg_bucket_span");
-        hipLaunchKernelGGL(k_agg_bucket_span, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, r,
-                           counts, words);
-    }
-    if (device_exclusive_scan(ctx, ItemsOf<unsigned long long>{counts}, n, offsets, block_sums, "k_agg_bucket_scan")) return 1;
+    const unsigned long long *offsets = nullptr;
+    unsigned int *words = nullptr;
     unsigned long long total = 0;
-    unsigned int span_error = 0;
-    MDB_HIP_CHECK(hipMemcpyAsync(&total, offsets + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipMemcpyAsync(&span_error, words, 4, hipMemcpyDeviceToHost, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    if (span_error & ERR_BUCKET_GROUP) return fail("A group id is not below n_groups.");
+    if (bucket_span_pairs(ctx, in, s, groups, r, &offsets, &words, &total)) return 1;
     if (total == 0) return 0;
+    void *p;
     // The MacaqueV streams of the batch's cursor index (built here for a batch the library holds; MDB_GRID_MV_INDEX=0:
     // none) go piece by piece: their entries are folded behind the pairs, in slices of their own.
     std::shared_ptr<MvIndex> index;
@@ -570,11 +577,7 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
                                          filter)) {
             return 1;
         }
-        if (m > 1) {
-            LaunchTimer timer(ctx, "k_agg_bucket_check");
-            hipLaunchKernelGGL(k_agg_bucket_check, dim3(blocks_for(m - 1)), dim3(BUCKET_THREADS), 0, ctx->stream, keys,
-                               m, words + 1);
-        }
+        bucket_keys_check(ctx, keys, m, words + 1);
         unsigned int read_back[2] = {0, 0};
         MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
         MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -587,23 +590,7 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
         tree.n[0] = m;
         tree.order = nullptr;
         if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            const uint64_t keys_bytes = align_up(m * 8, 256), order_bytes = align_up(m * 4, 256);
-            size_t sort_bytes = 0;
-            MDB_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, sort_bytes, keys, keys, static_cast<uint32_t *>(nullptr),
-                                                    static_cast<uint32_t *>(nullptr), (size_t)m, 0u, key_bits,
-                                                    ctx->stream));
-            if (scratch_reserve(ctx, SCRATCH_BUCKET_SORT, keys_bytes + 2 * order_bytes + sort_bytes, &p)) return 1;
-            Carver sort_scratch(p);
-            unsigned long long *sorted_keys = sort_scratch.take<unsigned long long>(m);
-            uint32_t *order_in = sort_scratch.take<uint32_t>(m);
-            uint32_t *order = sort_scratch.take<uint32_t>(m);
-            void *sort_storage = sort_scratch.at;
-            LaunchTimer timer(ctx, "k_agg_bucket_sort");
-            hipLaunchKernelGGL(k_agg_bucket_iota, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, order_in, m);
-            MDB_HIP_CHECK(rocprim::radix_sort_pairs(sort_storage, sort_bytes, keys, sorted_keys, order_in, order,
-                                                    (size_t)m, 0u, key_bits, ctx->stream));
-            tree.keys[0] = sorted_keys;
-            tree.order = order;
+            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
         }
         // The tree's levels over this slice, then the fold.
         tree.levels = 1;

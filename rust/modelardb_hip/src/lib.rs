@@ -33,7 +33,7 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
-    mdb_hist_request as HistRequest, mdb_value_filter as ValueFilter,
+    mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell, mdb_value_filter as ValueFilter,
 };
 pub use sys::MDB_HIST_MAX_EDGES;
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
@@ -341,6 +341,14 @@ fn check_bucket_cells(request: &BucketRequest, n_states: usize) -> Result<()> {
     Ok(())
 }
 
+/// `into[j]` merged with `from[j]` by the four rules of [`Context::m4_buckets`] (host arithmetic, no GPU).
+pub fn m4_merge(into: &mut [M4Cell], from: &[M4Cell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_m4_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
 /// The cells of a histogram call: `counts` is row-major `[n_groups][edges + 1]`.
 fn check_hist_cells(n_groups: u32, edges: &[f32], n_counts: usize) -> Result<()> {
     if (n_groups as u64) * (edges.len() as u64 + 1) != n_counts as u64 {
@@ -635,6 +643,51 @@ impl Context {
         check(unsafe {
             sys::mdb_agg_buckets_filter_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                              request, filter, states.as_mut_ptr())
+        })
+    }
+
+    /// M4 downsampling: per bucket of `date_bin(width, ts, origin)` and group the first, last, lowest and highest data
+    /// point with their timestamps, and the count, without materialising a data point. `cells` is row-major
+    /// `[n_groups][n_buckets]` (fresh: `M4Cell::default()`); the batch is merged into it by rules that depend on
+    /// nothing but the set of points, and a cell without points stays as it was. `request.which_mask` must be 0.
+    pub fn m4_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        cells: &mut [M4Cell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_m4_buckets(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::m4_buckets`] for several batches at once (rows in the order of the slice), merged as one batch.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn m4_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        cells: &mut [M4Cell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_m4_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32, request,
+                                     cells.as_mut_ptr())
         })
     }
 

@@ -233,6 +233,22 @@ pub struct mdb_hist_request {
     pub reserved: u32,
 }
 
+/// One cell of `mdb_m4_buckets*`: the first, last, lowest and highest point of a bucket and group with their
+/// timestamps, and the count. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty, no other member is read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_m4_cell {
+    pub count: i64,
+    pub t_first: i64,
+    pub t_last: i64,
+    pub t_min: i64,
+    pub t_max: i64,
+    pub v_first: f32,
+    pub v_last: f32,
+    pub v_min: f32,
+    pub v_max: f32,
+}
+
 #[link(name = "mdb_hip")]
 unsafe extern "C" {
     // ---- lifetime ----------------------------------------------------------------------------
@@ -364,6 +380,14 @@ unsafe extern "C" {
     pub fn mdb_hist_batch_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
                                group_of_segment: *const *const u32, n_inputs: u32, request: *const mdb_hist_request,
                                edges: *const f32, counts: *mut u64) -> c_int;
+    pub fn mdb_m4_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                          request: *const mdb_bucket_request, inout: *mut mdb_m4_cell) -> c_int;
+    pub fn mdb_m4_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                              request: *const mdb_bucket_request, inout: *mut mdb_m4_cell) -> c_int;
+    pub fn mdb_m4_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                               group_of_segment: *const *const u32, n_inputs: u32, request: *const mdb_bucket_request,
+                               inout: *mut mdb_m4_cell) -> c_int;
+    pub fn mdb_m4_merge_n(into: *mut mdb_m4_cell, from: *const mdb_m4_cell, n: u64) -> c_int;
     pub fn mdb_quantile_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
                               n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
@@ -482,3 +506,12 @@ const _: () = assert!(offset_of!(mdb_hist_request, n_edges) == 16);
 const _: () = assert!(offset_of!(mdb_hist_request, n_groups) == 20);
 const _: () = assert!(offset_of!(mdb_hist_request, flags) == 24);
 const _: () = assert!(offset_of!(mdb_hist_request, reserved) == 28);
+const _: () = assert!(size_of::<mdb_m4_cell>() == 56);
+const _: () = assert!(offset_of!(mdb_m4_cell, t_first) == 8);
+const _: () = assert!(offset_of!(mdb_m4_cell, t_last) == 16);
+const _: () = assert!(offset_of!(mdb_m4_cell, t_min) == 24);
+const _: () = assert!(offset_of!(mdb_m4_cell, t_max) == 32);
+const _: () = assert!(offset_of!(mdb_m4_cell, v_first) == 40);
+const _: () = assert!(offset_of!(mdb_m4_cell, v_last) == 44);
+const _: () = assert!(offset_of!(mdb_m4_cell, v_min) == 48);
+const _: () = assert!(offset_of!(mdb_m4_cell, v_max) == 52);
