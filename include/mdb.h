@@ -469,6 +469,48 @@ int mdb_m4_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const u
 /* Host arithmetic, no context, no GPU: into[j] merged with from[j] for j < n. */
 int mdb_m4_merge_n(mdb_m4_cell *into, const mdb_m4_cell *from, uint64_t n);
 
+/* Extension: variance and standard deviation - per bucket of date_bin(width, ts, origin) and group the count, the mean
+ * and m2 = the sum of (v - mean)^2: the state of DataFusion's variance accumulators, from which stddev, stddev_pop,
+ * var_samp and var_pop follow. The reference answers them with GridExec -> AggregateExec like a median: its
+ * model-based rule rewrites only count / min / max / sum / avg
+ * (crates/modelardb_storage/src/optimizer/model_simple_aggregates.rs:319-323), so every point is rebuilt first. Here
+ * the cells are computed on the segments and no point is materialised.
+ *   request: mdb_bucket_request, unchanged; which_mask must be 0. inout: row-major [n_groups][n_buckets] cells
+ *     (mdb_moments_cell, mdb_format.h); a fresh cell is all-zero bytes. group_of_segment as for mdb_agg_buckets.
+ *   Which points: exactly those mdb_agg_buckets counts for the same request, so count equals its COUNT, always.
+ *   How: a run of points (those of one segment in one bucket) is accumulated with sums shifted by the run's first
+ *     value K: d = (double)v - (double)K, s1 += d, s2 += d * d; mean = K + s1 / n, m2 = s2 - s1 * s1 / n (0 where
+ *     that rounds below 0). A sum of v * v next to the sum of v is not used: at a level of 1e6 with a deviation of 0.5
+ *     it loses four digits to cancellation. PMC-Mean on regular timestamps is (n, value, 0) in O(1); Swing is
+ *     evaluated point by point, because the rebuilt points are f32 roundings of the line and that rounding is part of
+ *     their variance.
+ *   Merge rule, the same in mdb_moments_merge_n and in every kernel: with n = na + nb and d = mean_b - mean_a,
+ *     mean = mean_a + d * (nb / n), m2 = m2_a + m2_b + d * d * (na * nb / n); an empty side gives the other side's
+ *     bytes. A call merges its batch into inout; a cell that receives no point keeps every byte it had. Cells of
+ *     equal values have m2 == 0.0 and mean == the value exactly, in any order of merges.
+ *   Non-finite points: in a cell that holds a NaN or an infinity count is exact and neither mean nor m2 is finite;
+ *     nothing more is promised.
+ *   Determinism, as for mdb_agg_buckets' SUM: for the same input, request and form two runs agree bit for bit, and so
+ *     do the host, dev and list forms; no float atomics, no atomics on cells. What changes the order of the merges -
+ *     MDB_AGG_BUCKET_SLICE_PAIRS, the order of the segments, cutting a batch into calls, whether the keys had to be
+ *     sorted - moves mean and m2 by rounding only (the tests allow 2^-44 of the largest |v| and 1e-5 of m2).
+ *   Errors (mdb_last_error set, inout untouched): those of mdb_m4_buckets - a NULL argument, which_mask != 0,
+ *     width <= 0, n_groups == 0, n_groups * n_buckets overflowing, a group id >= n_groups on any row, a malformed
+ *     segment among those the request reaches. An empty batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_moments_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                        const mdb_bucket_request *request, mdb_moments_cell *inout);
+/* All device pointers: the segments, group_of_segment and inout are in HBM. */
+int mdb_moments_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                            const mdb_bucket_request *request, mdb_moments_cell *inout);
+/* Several host batches (rows in the order of the list) folded as one batch, as mdb_agg_buckets_list does. */
+int mdb_moments_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                             uint32_t n_inputs, const mdb_bucket_request *request, mdb_moments_cell *inout);
+/* Host arithmetic, no context, no GPU: into[j] merged with from[j] by the merge rule, for j < n. */
+int mdb_moments_merge_n(mdb_moments_cell *into, const mdb_moments_cell *from, uint64_t n);
+/* Host arithmetic, no context, no GPU: variance_out[j] = m2 / (count - ddof) of cells[j]. ddof 0: var_pop (NaN for a
+ * count of 0); ddof 1: var_samp (NaN for a count of 1 or less); any other ddof is an error. stddev is its sqrt. */
+int mdb_moments_variance(const mdb_moments_cell *cells, uint64_t n, uint32_t ddof, double *variance_out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -208,6 +208,16 @@ typedef struct mdb_m4_cell {
     float   v_first, v_last, v_min, v_max;
 } mdb_m4_cell;             /* 56 bytes */
 
+/* One cell of mdb_moments_buckets*: the count, the mean and m2 = the sum of (v - mean)^2 over the points of a bucket
+ * and group - the state DataFusion's variance accumulators keep (count, mean, m2), from which var_pop, var_samp and
+ * the two stddev follow (mdb_moments_variance). A fresh cell is all-zero bytes. count == 0: the cell is empty and no
+ * other member is read; all are written when its first points arrive. */
+typedef struct mdb_moments_cell {
+    int64_t count;
+    double  mean;
+    double  m2;
+} mdb_moments_cell;        /* 24 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -306,5 +316,8 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_first) == 40);
 MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_last) == 44);
 MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_min) == 48);
 MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_max) == 52);
+MDB_LAYOUT_ASSERT(sizeof(mdb_moments_cell) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_moments_cell, mean) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_moments_cell, m2) == 16);
 
 #endif /* MDB_FORMAT_H */

@@ -197,6 +197,15 @@ class M4CellC(C.Structure):
     ]
 
 
+class MomentsCellC(C.Structure):
+    """mdb_moments_cell: the count, the mean and m2 = sum((v - mean)^2) of one bucket and group (mdb_moments_buckets*)."""
+    _fields_ = [
+        ("count", C.c_int64),
+        ("mean", C.c_double),
+        ("m2", C.c_double),
+    ]
+
+
 class HistRequestC(C.Structure):
     """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
     _fields_ = [
@@ -284,6 +293,14 @@ _HIP_SYMBOLS = {
     "mdb_m4_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
                                       C.POINTER(BucketRequestC), C.c_void_p]),
     "mdb_m4_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_moments_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                      C.c_void_p]),
+    "mdb_moments_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                          C.c_void_p]),
+    "mdb_moments_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                           C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_moments_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_moments_variance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_grid_count_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC),
                                             C.POINTER(C.c_uint64)]),
     "mdb_grid_batch_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_void_p,

@@ -164,6 +164,46 @@ def m4_merge(into, from_):
     return into
 
 
+# mdb_moments_cell as a numpy record: the cells of mdb_moments_buckets*, row-major [n_groups][n_buckets].
+MOMENTS_CELL_DTYPE = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8")])
+assert MOMENTS_CELL_DTYPE.itemsize == C.sizeof(_abi.MomentsCellC)
+
+
+def fresh_moments_cells(shape):
+    """Fresh (empty) moments cells: all-zero bytes."""
+    return np.zeros(shape, dtype=MOMENTS_CELL_DTYPE)
+
+
+def moments_merge(into, from_):
+    """into[k] merged with from_[k] in place by the merge rule of mdb_moments_buckets (mdb_moments_merge_n): two
+    arrays of MOMENTS_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != MOMENTS_CELL_DTYPE or from_.dtype != MOMENTS_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("moments_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("moments_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_moments_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def moments_variance(cells, ddof=1):
+    """m2 / (count - ddof) per cell (mdb_moments_variance): ddof 0 is var_pop, 1 var_samp; NaN where the count does not
+    allow it. The standard deviation is its np.sqrt. Returns float64 of the shape of `cells`."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != MOMENTS_CELL_DTYPE:
+        raise ValueError("moments_variance takes an array of MOMENTS_CELL_DTYPE")
+    if ddof < 0:
+        raise ValueError("ddof must be 0 or 1")
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if lib.mdb_moments_variance(flat.ctypes.data_as(C.c_void_p), flat.size, int(ddof),
+                                out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -936,6 +976,77 @@ class Context:
             if dev_groups is not None:
                 self.dev_free(dev_groups)
         return cells
+
+    # ---- variance and standard deviation: count, mean and m2 per time bucket --------------------------
+
+    @staticmethod
+    def _moments_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_moments_cells((n_groups, n_buckets))
+        if cells.dtype != MOMENTS_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of MOMENTS_CELL_DTYPE")
+        return cells
+
+    def moments_buckets(self, batch, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                        n_groups=None):
+        """The count, the mean and m2 = sum((v - mean)^2) per bucket of date_bin(width, ts, origin) and group
+        (mdb_moments_buckets): returns `cells` (or fresh ones), shape (n_groups, n_buckets), merged in place.
+        `groups` and n_groups as for agg_buckets; moments_variance turns cells into variances."""
+        return self.moments_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups],
+                                         t_lo, t_hi, cells, n_groups)
+
+    def moments_buckets_list(self, batches, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                             n_groups=None):
+        """Several host batches merged as one (mdb_moments_buckets_list); `groups`: None or one array (or None) per
+        batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._moments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_moments_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                      C.byref(request), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def moments_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                            cells=None, n_groups=None):
+        """mdb_moments_buckets_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded
+        again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._moments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_moments_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                         None if dev_groups is None else C.c_void_p(dev_groups),
+                                                         C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, MOMENTS_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def moments(self, batch, t_lo=None, t_hi=None, groups=None, n_groups=None):
+        """The cells of the points of `batch` inside [t_lo, t_hi], one per group (shape (n_groups,)): one bucket over
+        the data inside the range, what a whole-batch stddev / variance query needs."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        if len(batch) == 0:
+            return fresh_moments_cells(n_groups)
+        lo, hi = int(np.min(batch.start_time)), int(np.max(batch.end_time))
+        lo = lo if t_lo is None else max(lo, int(t_lo))
+        hi = hi if t_hi is None else min(hi, int(t_hi))
+        if lo > hi:
+            return fresh_moments_cells(n_groups)
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the data inside the range spans more than one bucket can hold: use moments_buckets")
+        return self.moments_buckets(batch, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
 
     @staticmethod
     def _n_groups(n_groups, states, groups):

@@ -33,7 +33,8 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
-    mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell, mdb_value_filter as ValueFilter,
+    mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell, mdb_moments_cell as MomentsCell,
+    mdb_value_filter as ValueFilter,
 };
 pub use sys::MDB_HIST_MAX_EDGES;
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
@@ -347,6 +348,23 @@ pub fn m4_merge(into: &mut [M4Cell], from: &[M4Cell]) -> Result<()> {
         return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
     }
     check(unsafe { sys::mdb_m4_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// `into[j]` merged with `from[j]` by the merge rule of [`Context::moments_buckets`] (host arithmetic, no GPU): what
+/// a `VarianceAccumulator`-shaped accumulator does in `merge_batch`.
+pub fn moments_merge(into: &mut [MomentsCell], from: &[MomentsCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_moments_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// `m2 / (count - ddof)` per cell (host arithmetic, no GPU): `ddof` 0 is `var_pop`, 1 `var_samp`; NaN where the count
+/// does not allow it. The standard deviation is its `sqrt`.
+pub fn moments_variance(cells: &[MomentsCell], ddof: u32) -> Result<Vec<f64>> {
+    let mut variance = vec![0.0f64; cells.len()];
+    check(unsafe { sys::mdb_moments_variance(cells.as_ptr(), cells.len() as u64, ddof, variance.as_mut_ptr()) })?;
+    Ok(variance)
 }
 
 /// The cells of a histogram call: `counts` is row-major `[n_groups][edges + 1]`.
@@ -688,6 +706,51 @@ impl Context {
         check(unsafe {
             sys::mdb_m4_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32, request,
                                      cells.as_mut_ptr())
+        })
+    }
+
+    /// Variance and standard deviation: per bucket of `date_bin(width, ts, origin)` and group the count, the mean and
+    /// `m2`, the sum of `(v - mean)^2`, without materialising a data point. `cells` is row-major `[n_groups][n_buckets]`
+    /// (fresh: `MomentsCell::default()`); the batch is merged into it, and a cell without points stays as it was.
+    /// `request.which_mask` must be 0. [`moments_variance`] turns cells into variances.
+    pub fn moments_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        cells: &mut [MomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_moments_buckets(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::moments_buckets`] for several batches at once (rows in the order of the slice), merged as one batch.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn moments_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        cells: &mut [MomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_moments_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                          request, cells.as_mut_ptr())
         })
     }
 

@@ -249,6 +249,17 @@ pub struct mdb_m4_cell {
     pub v_max: f32,
 }
 
+/// One cell of `mdb_moments_buckets*`: the count, the mean and `m2`, the sum of `(v - mean)^2`, of a bucket and group:
+/// the state of DataFusion's variance accumulators. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty,
+/// no other member is read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_moments_cell {
+    pub count: i64,
+    pub mean: f64,
+    pub m2: f64,
+}
+
 #[link(name = "mdb_hip")]
 unsafe extern "C" {
     // ---- lifetime ----------------------------------------------------------------------------
@@ -388,6 +399,15 @@ unsafe extern "C" {
                                group_of_segment: *const *const u32, n_inputs: u32, request: *const mdb_bucket_request,
                                inout: *mut mdb_m4_cell) -> c_int;
     pub fn mdb_m4_merge_n(into: *mut mdb_m4_cell, from: *const mdb_m4_cell, n: u64) -> c_int;
+    pub fn mdb_moments_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                               request: *const mdb_bucket_request, inout: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_moments_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                   request: *const mdb_bucket_request, inout: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_moments_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                    group_of_segment: *const *const u32, n_inputs: u32,
+                                    request: *const mdb_bucket_request, inout: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_moments_merge_n(into: *mut mdb_moments_cell, from: *const mdb_moments_cell, n: u64) -> c_int;
+    pub fn mdb_moments_variance(cells: *const mdb_moments_cell, n: u64, ddof: u32, variance_out: *mut f64) -> c_int;
     pub fn mdb_quantile_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
                               n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
@@ -515,3 +535,6 @@ const _: () = assert!(offset_of!(mdb_m4_cell, v_first) == 40);
 const _: () = assert!(offset_of!(mdb_m4_cell, v_last) == 44);
 const _: () = assert!(offset_of!(mdb_m4_cell, v_min) == 48);
 const _: () = assert!(offset_of!(mdb_m4_cell, v_max) == 52);
+const _: () = assert!(size_of::<mdb_moments_cell>() == 24);
+const _: () = assert!(offset_of!(mdb_moments_cell, mean) == 8);
+const _: () = assert!(offset_of!(mdb_moments_cell, m2) == 16);
