@@ -511,6 +511,71 @@ int mdb_moments_merge_n(mdb_moments_cell *into, const mdb_moments_cell *from, ui
  * count of 0); ddof 1: var_samp (NaN for a count of 1 or less); any other ddof is an error. stddev is its sqrt. */
 int mdb_moments_variance(const mdb_moments_cell *cells, uint64_t n, uint32_t ddof, double *variance_out);
 
+/* Extension: value histograms and exact quantiles PER BUCKET of date_bin(width, ts, origin) and group -
+ *   SELECT date_bin(...), approx_percentile_cont(field, 0.95) ... GROUP BY 1 / median(field) per bucket / a heat map
+ *   (time bucket x value cell),
+ * which the reference answers with GridExec -> AggregateExec GROUP BY the date_bin, every point rebuilt first: its
+ * model-based rule rewrites only count / min / max / sum / avg and only without a GROUP BY on time
+ * (crates/modelardb_storage/src/optimizer/model_simple_aggregates.rs:319-323), so it rewrites neither the percentile
+ * nor the grouping. mdb_hist_batch / mdb_quantile_batch answer it for ONE time range a call; these answer every bucket
+ * in one call.
+ *   request: mdb_bucket_request, unchanged; which_mask must be 0. group_of_segment as for mdb_agg_buckets.
+ *   edges, cells: those of mdb_hist_batch - 1 .. MDB_HIST_MAX_EDGES edges, strictly increasing in totalOrder, the cell
+ *     of a value = the number of edges at or below it; n_cells = n_edges + 1.
+ *   counts: uint64_t [n_groups][n_buckets][n_cells], row-major. A call ADDS to them; a cell that receives nothing keeps
+ *     its bytes; they are touched only once the pass is known to be free of errors.
+ *   Which points: exactly those mdb_agg_buckets counts for the same request - bucket floor((t - origin) / width) in
+ *     [0, n_buckets), t in [t_lo, t_hi], segment row i in group group_of_segment[i]. Per (group, bucket) the cells'
+ *     increments add up to that operator's COUNT, always.
+ *   Cost: one pass. PMC-Mean on regular timestamps is one addition per (segment, bucket); Swing on regular timestamps
+ *     the binary searches of mdb_hist_batch per (segment, bucket); a stream of VALUES (MacaqueV, a residual tail) is
+ *     decoded once however many buckets its segment reaches. Irregular TIMESTAMPS are decoded a constant number of
+ *     times per pass, not once: once by the segment's analysis, once to place the points, and under values in a bit
+ *     stream once more where a model precedes a residual tail (three times, so twelve per mdb_quantile_buckets call);
+ *     such segments also take 8 bytes of scratch per bucket they reach. Only a malformed stream whose timestamps are
+ *     not sorted is walked bucket by bucket.
+ *   Determinism: integers only (integer atomics on zeroed scratch): the three forms and any two runs agree bit for
+ *     bit.
+ *   Errors (mdb_last_error set, counts untouched): a NULL argument; which_mask != 0; a bad edge list; width <= 0;
+ *     n_groups == 0; n_groups * n_buckets * n_cells overflowing or not fitting the device's memory; a group id >=
+ *     n_groups on ANY row, also one the request does not reach; a malformed segment among those the request reaches.
+ *     An empty batch, n_buckets == 0 or an empty time range succeeds and changes nothing.
+ *     "Not fitting" is judged against the device's TOTAL memory, as mdb_hist_batch does: counters between what is free
+ *     and the total fail in the allocation instead, with the allocator's message - counts untouched either way. The
+ *     same holds for the windows of mdb_quantile_buckets. */
+int mdb_hist_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                     const mdb_bucket_request *request, const float *edges, uint32_t n_edges, uint64_t *counts);
+/* The segments, group_of_segment and counts are in HBM; request and edges are host pointers. */
+int mdb_hist_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                         const mdb_bucket_request *request, const float *edges, uint32_t n_edges, uint64_t *counts);
+/* Several host batches (rows in the order of the list) counted as one batch; group_of_segment[k] (or NULL) per batch. */
+int mdb_hist_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                          uint32_t n_inputs, const mdb_bucket_request *request, const float *edges, uint32_t n_edges,
+                          uint64_t *counts);
+/* Exact order statistics of every (group, bucket) cell, in totalOrder: out_lo / out_hi are float
+ * [n_groups][n_buckets][n_q], n_points uint64_t [n_groups][n_buckets] (written for every cell). For a cell of N points
+ * and q[i] in [0, 1]: p = q[i] * (double)(N - 1), out_lo = the floor(p)-th smallest point of the cell (0-based), out_hi
+ * the ceil(p)-th (mdb_quantile_positions). A cell with N == 0 leaves its out_lo / out_hi entries untouched.
+ * Interpolation is the caller's. 1 <= n_q <= MDB_QUANTILE_BUCKETS_MAX_Q.
+ * How: a radix selection on the 32-bit keys, 8 + 8 + 8 + 8 bits, with a window of 256 counters per (cell, rank):
+ * MDB_QUANTILE_BUCKETS_PASSES passes over the resident batch (the host form uploads it once) serve every cell and
+ * every rank, whatever their number; the digit of a rank is chosen on the device, only n_points and the final keys
+ * come back. Counters: n_groups * n_buckets * 2 n_q * 256 * 8 bytes of scratch. The cells of a later pass are narrow
+ * (2^16, 2^8, then one key), so the closed form of a Swing segment on regular timestamps - binary searches per cell it
+ * crosses - gives way to point-by-point evaluation there: a Swing segment costs O(points) per pass from the second
+ * pass on, where the histogram costs O(cells crossed * log points).
+ * Errors (outputs untouched): those of mdb_hist_buckets (without the edges; the counters are the windows), q outside
+ * [0, 1] or NaN, n_q out of range. An empty batch writes n_points = 0 everywhere and nothing else. */
+#define MDB_QUANTILE_BUCKETS_MAX_Q 4u
+#define MDB_QUANTILE_BUCKETS_PASSES 4u
+int mdb_quantile_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                         const mdb_bucket_request *request, const double *q, uint32_t n_q, float *out_lo, float *out_hi,
+                         uint64_t *n_points);
+/* The segments and group_of_segment are in HBM; the outputs are host pointers. */
+int mdb_quantile_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                             const mdb_bucket_request *request, const double *q, uint32_t n_q, float *out_lo,
+                             float *out_hi, uint64_t *n_points);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

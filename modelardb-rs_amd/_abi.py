@@ -219,6 +219,8 @@ class HistRequestC(C.Structure):
 
 
 MDB_HIST_MAX_EDGES = 4095
+MDB_QUANTILE_BUCKETS_MAX_Q = 4
+MDB_QUANTILE_BUCKETS_PASSES = 4
 
 _HIP_SYMBOLS = {
     # name: (restype, argtypes)
@@ -345,6 +347,16 @@ _HIP_SYMBOLS = {
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "mdb_quantile_batch_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_int64, C.c_int64, C.c_void_p, C.c_uint32,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "mdb_hist_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC), C.c_void_p,
+                                   C.c_uint32, C.c_void_p]),
+    "mdb_hist_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                       C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_hist_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                        C.POINTER(BucketRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_quantile_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mdb_quantile_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mdb_hist_cell_of": (C.c_int, [C.c_void_p, C.c_uint32, C.c_float, C.POINTER(C.c_uint32)]),
     "mdb_quantile_positions": (C.c_int, [C.c_double, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                          C.POINTER(C.c_double)]),

@@ -1145,6 +1145,112 @@ class Context:
         """quantile on a resident batch (mdb_quantile_batch_dev)."""
         return self._quantile(self.lib.mdb_quantile_batch_dev, dev_segments.seg, q, t_lo, t_hi, interpolate)
 
+    # ---- value histograms and quantiles per time bucket ---------------------------------------------
+
+    @staticmethod
+    def _hist_bucket_counts(counts, n_groups, n_buckets, n_cells):
+        if counts is None:
+            return np.zeros((n_groups, n_buckets, n_cells), dtype=np.uint64)
+        if counts.dtype != np.uint64 or counts.shape != (n_groups, n_buckets, n_cells) or not counts.flags.c_contiguous:
+            raise ValueError(f"counts must be a contiguous ({n_groups}, {n_buckets}, {n_cells}) array of uint64")
+        return counts
+
+    def hist_buckets(self, batch, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, counts=None,
+                     n_groups=None):
+        """The points of `batch` ADDED to `counts` (or to fresh zeros), shape (n_groups, n_buckets, len(edges) + 1): per
+        bucket of date_bin(width, ts, origin) and group the histogram `hist` gives for one range (mdb_hist_buckets).
+        `groups` and n_groups as for agg_buckets."""
+        return self.hist_buckets_list([batch], edges, origin, width, n_buckets, None if groups is None else [groups],
+                                      t_lo, t_hi, counts, n_groups)
+
+    def hist_buckets_list(self, batches, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                          counts=None, n_groups=None):
+        """Several host batches counted as one (mdb_hist_buckets_list); `groups`: None or one array (or None) per
+        batch."""
+        edges = _edges_array(edges)
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, counts, batch_groups)
+        counts = self._hist_bucket_counts(counts, n_groups, n_buckets, len(edges) + 1)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_hist_buckets_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                   edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                   counts.ctypes.data_as(C.c_void_p)))
+        return counts
+
+    def hist_buckets_dev(self, dev_segments, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                         counts=None, n_groups=None):
+        """mdb_hist_buckets_dev on a resident batch: `groups` and `counts` are uploaded, the counts downloaded again."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, counts, [groups])
+        counts = self._hist_bucket_counts(counts, n_groups, n_buckets, len(edges) + 1)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_counts = self.upload_array(counts)
+        try:
+            self._check(self.lib.mdb_hist_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                      None if dev_groups is None else C.c_void_p(dev_groups),
+                                                      C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                      C.c_void_p(dev_counts)))
+            counts[...] = self.download_array(dev_counts, counts.size, np.uint64).reshape(counts.shape)
+        finally:
+            self.dev_free(dev_counts)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return counts
+
+    def _quantile_buckets(self, call, seg, groups, q, origin, width, n_buckets, n_groups, t_lo, t_hi, interpolate):
+        q = np.atleast_1d(np.ascontiguousarray(q, dtype=np.float64))
+        shape = (n_groups, n_buckets, len(q))
+        lo = np.full(shape, np.nan, dtype=np.float32)
+        hi = np.full(shape, np.nan, dtype=np.float32)
+        n_points = np.zeros((n_groups, n_buckets), dtype=np.uint64)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        self._check(call(self.handle, C.byref(seg), groups, C.byref(request), q.ctypes.data_as(C.c_void_p), len(q),
+                         lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
+                         n_points.ctypes.data_as(C.c_void_p)))
+        if not interpolate:
+            return lo, hi, n_points
+        last = np.maximum(n_points, 1).astype(np.float64) - 1.0
+        positions = q[None, None, :] * last[:, :, None]  # (p = q * (double)(N - 1), as mdb_quantile_positions)
+        fractions = positions - np.floor(positions)
+        wide_lo, wide_hi = lo.astype(np.float64), hi.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            # (equal ends - also infinite ones - are the value itself: no inf - inf; a cell without a point stays NaN)
+            values = np.where(lo.view(np.uint32) == hi.view(np.uint32), wide_lo, wide_lo + (wide_hi - wide_lo) * fractions)
+        return values, n_points
+
+    def quantile_buckets(self, batch, q, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, n_groups=None,
+                         interpolate=False):
+        """Exact order statistics per bucket of date_bin(width, ts, origin) and group (mdb_quantile_buckets): (lo, hi,
+        n_points) with lo / hi of shape (n_groups, n_buckets, len(q)) - the floor / ceil ranks of q[i] * (N - 1) among
+        the cell's N points, NaN-filled where N == 0 - and n_points of shape (n_groups, n_buckets). interpolate=True:
+        (lo + (hi - lo) * fraction in f64, n_points), as `quantile`. At most MDB_QUANTILE_BUCKETS_MAX_Q quantiles."""
+        groups = self._groups_array(groups, len(batch))
+        n_groups = self._n_groups(n_groups, None, [groups])
+        pointer = None if groups is None else groups.ctypes.data_as(C.c_void_p)
+        return self._quantile_buckets(self.lib.mdb_quantile_buckets, batch.as_c(), pointer, q, origin, width, n_buckets,
+                                      n_groups, t_lo, t_hi, interpolate)
+
+    def quantile_buckets_dev(self, dev_segments, q, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                             n_groups=None, interpolate=False):
+        """quantile_buckets on a resident batch (mdb_quantile_buckets_dev): `groups` is uploaded."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, None, [groups])
+        dev_groups = None if groups is None else self.upload_array(groups)
+        try:
+            return self._quantile_buckets(self.lib.mdb_quantile_buckets_dev, dev_segments.seg,
+                                          None if dev_groups is None else C.c_void_p(dev_groups), q, origin, width,
+                                          n_buckets, n_groups, t_lo, t_hi, interpolate)
+        finally:
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+
     # ---- fit -------------------------------------------------------------------------------------
 
     def compress_chunks(self, timestamps, values, chunk_offsets, eb):

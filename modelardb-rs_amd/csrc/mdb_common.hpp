@@ -95,6 +95,8 @@ enum ScratchSlot {
     SCRATCH_MASK_SEGMENTS,   // mdb_mask_* / mdb_*_mask*: per segment its rows, first row, class, counts and the scans
     SCRATCH_MASK_WORDS,      // ... the masks of the host forms (mdb_*_where*)
     SCRATCH_HIST_CELLS,      // mdb_hist_* / mdb_quantile_*: the zeroed cells of one pass, the edges' keys, the error word
+    SCRATCH_HIST_BUCKET_OFFSETS, // mdb_hist_buckets* / mdb_quantile_buckets*: slot offsets per segment and their scan
+    SCRATCH_HIST_BUCKET_SLOTS,   // ... the index interval per (segment, bucket) of irregular timestamps under a bit stream
     SCRATCH_SLOT_COUNT
 };
 

@@ -25,105 +25,11 @@
 // cells pin an order statistic of the 32-bit keys exactly.
 #include "mdb_hist.hpp"
 
-#include "mdb_agg_dev.hpp"
-#include "mdb_filter.hpp"
-#include "mdb_segment_dev.hpp"
+#include "mdb_hist_dev.hpp"
 
 #include <vector>
 
 namespace mdb {
-
-constexpr int HIST_THREADS = 256;
-constexpr uint32_t ERR_HIST_GROUP = 1u << 31; // a group id >= n_groups
-
-// What one lane of k_hist carries from point to point.
-struct HistLane {
-    const int32_t *edges;      // the edges' keys (LDS)
-    uint32_t n_edges;
-    unsigned long long *cells; // the row of the segment's group
-    int32_t lo, hi;            // the keys of the current cell, closed (lo > hi: no cell yet)
-    uint32_t cell;
-    unsigned long long run;    // points of the current cell not added yet
-
-    // The number of edges at or below `key`.
-    __device__ __forceinline__ uint32_t cell_of(int32_t key) const {
-        uint32_t a = 0, b = n_edges;
-        while (a < b) {
-            const uint32_t mid = a + (b - a) / 2;
-            if (edges[mid] <= key) a = mid + 1;
-            else b = mid;
-        }
-        return a;
-    }
-    __device__ __forceinline__ void flush() {
-        if (run) atomicAdd(&cells[cell], run);
-        run = 0;
-    }
-    // n points of key `key` (n may be 0: the lane's cell becomes the key's).
-    __device__ __forceinline__ void add(int32_t key, unsigned long long n) {
-        if (key < lo || key > hi) {
-            flush();
-            cell = cell_of(key);
-            lo = cell == 0 ? INT32_MIN : edges[cell - 1];
-            hi = cell == n_edges ? INT32_MAX : edges[cell] - 1; // (edges[cell] > key: no wrap)
-        }
-        run += n;
-    }
-};
-
-// The selector of segment_range (mdb_filter.hpp) that counts into cells: counts() records the point and selects
-// nothing (the walk's RangeAcc stays empty), model() is the closed form over the model points [a, b].
-struct HistCells {
-    static constexpr bool by_row = false;
-    HistLane *lane;
-    __device__ __forceinline__ bool counts(float v, uint64_t) const {
-        lane->add(total_order_key(__float_as_uint(v)), 1);
-        return false;
-    }
-    __device__ __forceinline__ void model(const SegDesc &d, uint32_t type, uint32_t a, uint32_t b, uint64_t,
-                                          RangeAcc &) const {
-        HistLane &l = *lane;
-        const uint32_t n = b - a + 1;
-        if (type == MDB_PMC_MEAN_ID) {
-            l.add(total_order_key(__float_as_uint(d.value)), n);
-            return;
-        }
-        auto key_at = [&](uint32_t k) { return total_order_key(__float_as_uint(swing_value_at(d, k))); };
-        auto point_by_point = [&]() {
-            for (uint32_t k = a;; k++) {
-                l.add(key_at(k), 1);
-                if (k == b) break;
-            }
-        };
-        const float va = swing_value_at(d, a), vb = swing_value_at(d, b);
-        if (va != va || vb != vb) return point_by_point(); // (as ValueKeys::model: the run is not known to be sorted)
-        const int32_t ka = total_order_key(__float_as_uint(va)), kb = total_order_key(__float_as_uint(vb));
-        const uint32_t ca = l.cell_of(ka), cb = l.cell_of(kb);
-        if (ca == cb) { // (slope 0, or a line that stays inside one cell: the keys between the ends lie between them)
-            l.add(ka, n);
-            return;
-        }
-        const uint32_t crossed = ca < cb ? cb - ca : ca - cb;
-        const uint32_t steps = 32u - (uint32_t)__clz(n - 1); // ceil(log2(n)), n >= 2 here: the steps of one search
-        if ((uint64_t)crossed * steps > n) return point_by_point();
-        // The keys are sorted along k (model_run): walk from the first end's cell to the last end's, each crossed edge's
-        // first index found by one binary search.
-        const bool up = ka < kb;
-        uint32_t at = a;
-        while (at <= b) {
-            l.add(key_at(at), 0);
-            if (l.cell == cb) {
-                l.run += b + 1 - at;
-                break;
-            }
-            const int32_t lo = l.lo, hi = l.hi;
-            const uint32_t next = up ? swing_first_past(d, at + 1, b + 1, [&](int32_t key) { return key > hi; })
-                                     : swing_first_past(d, at + 1, b + 1, [&](int32_t key) { return key < lo; });
-            l.run += next - at;
-            at = next;
-        }
-    }
-};
 
 __global__ __launch_bounds__(HIST_THREADS) void k_hist_groups(const uint32_t *__restrict__ groups, uint64_t n,
                                                               uint32_t n_groups, unsigned int *__restrict__ error) {
@@ -178,11 +84,17 @@ __global__ __launch_bounds__(HIST_THREADS) void k_hist_fold(const unsigned long 
     }
 }
 
-namespace {
-
-uint32_t hist_blocks(uint64_t n) { // grid-stride beyond 8 workgroups per CU, as the aggregates
-    return (uint32_t)std::min<uint64_t>((n + HIST_THREADS - 1) / HIST_THREADS, 256 * 8);
+void hist_groups_launch(mdb_ctx *ctx, const uint32_t *groups, uint64_t n, uint32_t n_groups, unsigned int *error) {
+    LaunchTimer timer(ctx, "k_hist_groups");
+    hipLaunchKernelGGL(k_hist_groups, dim3(hist_blocks(n)), dim3(HIST_THREADS), 0, ctx->stream, groups, n, n_groups, error);
 }
+
+void hist_fold_launch(mdb_ctx *ctx, const unsigned long long *cells, uint64_t n, unsigned long long *counts) {
+    LaunchTimer timer(ctx, "k_hist_fold");
+    hipLaunchKernelGGL(k_hist_fold, dim3(hist_blocks(n)), dim3(HIST_THREADS), 0, ctx->stream, cells, n, counts);
+}
+
+namespace {
 
 struct HistRequest { // a checked mdb_hist_request with its edges as keys
     int64_t t_lo, t_hi;
@@ -226,11 +138,7 @@ int hist_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, const
     MDB_HIP_CHECK(hipMemsetAsync(cells, 0, total * 8, ctx->stream));
     MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
     MDB_HIP_CHECK(mail_write(ctx, edge_keys, r.edge_keys.data(), r.edge_keys.size() * 4));
-    if (groups) {
-        LaunchTimer timer(ctx, "k_hist_groups");
-        hipLaunchKernelGGL(k_hist_groups, dim3(hist_blocks(n)), dim3(HIST_THREADS), 0, ctx->stream, groups, n, r.n_groups,
-                           words);
-    }
+    if (groups) hist_groups_launch(ctx, groups, n, r.n_groups, words);
     {
         LaunchTimer timer(ctx, "k_hist");
         hipLaunchKernelGGL(k_hist, dim3(hist_blocks(n)), dim3(HIST_THREADS), 0, ctx->stream, to_dev(in), groups, r.t_lo,
@@ -249,11 +157,7 @@ int hist_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, const
         for (uint64_t j = 0; j < total; j++) host_counts[j] += added[j];
         return 0;
     }
-    {
-        LaunchTimer timer(ctx, "k_hist_fold");
-        hipLaunchKernelGGL(k_hist_fold, dim3(hist_blocks(total)), dim3(HIST_THREADS), 0, ctx->stream, cells, total,
-                           dev_counts);
-    }
+    hist_fold_launch(ctx, cells, total, dev_counts);
     MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     MDB_HIP_CHECK(hipGetLastError());
     return 0;

@@ -36,7 +36,7 @@ pub use sys::{
     mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell, mdb_moments_cell as MomentsCell,
     mdb_value_filter as ValueFilter,
 };
-pub use sys::MDB_HIST_MAX_EDGES;
+pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
 pub use sys::{MDB_AGG_AVG, MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM};
@@ -373,6 +373,18 @@ fn check_hist_cells(n_groups: u32, edges: &[f32], n_counts: usize) -> Result<()>
         return Err(HipError(format!(
             "counts holds {} cells, the request n_groups * (edges + 1) = {} * {}",
             n_counts, n_groups, edges.len() + 1
+        )));
+    }
+    Ok(())
+}
+
+/// The cells of a per-bucket histogram call: `counts` is row-major `[n_groups][n_buckets][n_cells]`.
+fn check_hist_bucket_cells(request: &BucketRequest, n_cells: u64, n_counts: usize) -> Result<()> {
+    let wanted = (request.n_groups as u64).checked_mul(request.n_buckets).and_then(|rows| rows.checked_mul(n_cells));
+    if wanted != Some(n_counts as u64) {
+        return Err(HipError(format!(
+            "counts holds {} cells, the request n_groups * n_buckets * (edges + 1) = {} * {} * {}",
+            n_counts, request.n_groups, request.n_buckets, n_cells
         )));
     }
     Ok(())
@@ -805,6 +817,92 @@ impl Context {
             sys::mdb_hist_batch_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                      &request, edges.as_ptr(), counts.as_mut_ptr())
         })
+    }
+
+    /// [`Context::hist`] per bucket of `date_bin(width, ts, origin)` and group, in one pass: `counts` is row-major
+    /// `[n_groups][n_buckets][edges.len() + 1]` and the points `Context::agg_buckets` counts for the same request are
+    /// ADDED to it. `request.which_mask` must be 0.
+    pub fn hist_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        edges: &[f32],
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_hist_bucket_cells(request, edges.len() as u64 + 1, counts.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_hist_buckets(self.raw(), &segments.raw, groups, request, edges.as_ptr(), n_edges, counts.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::hist_buckets`] for several batches at once (rows in the order of the slice), counted as one batch.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn hist_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        edges: &[f32],
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_hist_bucket_cells(request, edges.len() as u64 + 1, counts.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_hist_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                       request, edges.as_ptr(), n_edges, counts.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::quantile`] per bucket of `date_bin(width, ts, origin)` and group, in
+    /// [`MDB_QUANTILE_BUCKETS_PASSES`] passes whatever the number of cells: row-major `[n_groups][n_buckets]` entries,
+    /// each `None` for a cell without a point, else the `(lo, hi)` order statistics of every `q` and the cell's number
+    /// of points. At most [`MDB_QUANTILE_BUCKETS_MAX_Q`] quantiles per call; `request.which_mask` must be 0.
+    pub fn quantile_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        q: &[f64],
+    ) -> Result<Vec<Option<(Vec<(f32, f32)>, u64)>>> {
+        check_group_ids(segments, group_of_segment)?;
+        let cells = (request.n_groups as u64).checked_mul(request.n_buckets)
+            .and_then(|cells| usize::try_from(cells).ok())
+            .and_then(|cells| cells.checked_mul(q.len().max(1)).map(|_| cells))
+            .ok_or_else(|| HipError("n_groups * n_buckets * n_q overflows".to_string()))?;
+        let (mut lo, mut hi) = (vec![0f32; cells * q.len()], vec![0f32; cells * q.len()]);
+        let mut n_points = vec![0u64; cells];
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let n_q = u32::try_from(q.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_quantile_buckets(self.raw(), &segments.raw, groups, request, q.as_ptr(), n_q, lo.as_mut_ptr(),
+                                      hi.as_mut_ptr(), n_points.as_mut_ptr())
+        })?;
+        Ok((0..cells)
+            .map(|cell| {
+                if n_points[cell] == 0 {
+                    return None;
+                }
+                let at = cell * q.len();
+                Some((lo[at..at + q.len()].iter().copied().zip(hi[at..at + q.len()].iter().copied()).collect(),
+                      n_points[cell]))
+            })
+            .collect())
     }
 
     /// Exact order statistics of the values of `segments` inside `time_range`, in totalOrder: for every `q` in

@@ -213,6 +213,10 @@ pub struct mdb_value_filter {
 
 /// Most edges of one histogram: 4 096 cells, 16 KB of keys in LDS, three passes cover the 32-bit keys.
 pub const MDB_HIST_MAX_EDGES: u32 = 4095;
+/// Most quantiles of one `mdb_quantile_buckets*` call, and the passes over the batch such a call makes (8 + 8 + 8 + 8
+/// bits of the 32-bit keys), whatever the number of cells and ranks.
+pub const MDB_QUANTILE_BUCKETS_MAX_Q: u32 = 4;
+pub const MDB_QUANTILE_BUCKETS_PASSES: u32 = 4;
 
 /// A value histogram for `mdb_hist_batch*`: `n_edges` edges (strictly increasing in the totalOrder of
 /// `mdb_value_filter`) cut the values into `n_edges + 1` cells; a point falls in the cell numbered by the edges at or
@@ -412,6 +416,22 @@ unsafe extern "C" {
                               n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
                                   n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
+    // ---- histograms and exact quantiles per date_bin bucket and group (include/mdb.h) ----
+    pub fn mdb_hist_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                            request: *const mdb_bucket_request, edges: *const f32, n_edges: u32, counts: *mut u64)
+                            -> c_int;
+    pub fn mdb_hist_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                request: *const mdb_bucket_request, edges: *const f32, n_edges: u32, counts: *mut u64)
+                                -> c_int;
+    pub fn mdb_hist_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                 group_of_segment: *const *const u32, n_inputs: u32, request: *const mdb_bucket_request,
+                                 edges: *const f32, n_edges: u32, counts: *mut u64) -> c_int;
+    pub fn mdb_quantile_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                request: *const mdb_bucket_request, q: *const f64, n_q: u32, out_lo: *mut f32,
+                                out_hi: *mut f32, n_points: *mut u64) -> c_int;
+    pub fn mdb_quantile_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                    request: *const mdb_bucket_request, q: *const f64, n_q: u32, out_lo: *mut f32,
+                                    out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_hist_cell_of(edges: *const f32, n_edges: u32, value: f32, cell: *mut u32) -> c_int;
     pub fn mdb_quantile_positions(q: f64, n_points: u64, rank_lo: *mut u64, rank_hi: *mut u64,
                                   fraction: *mut f64) -> c_int;
