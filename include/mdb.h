@@ -62,7 +62,10 @@ int mdb_trim(mdb_ctx *ctx, uint64_t *released_bytes);
 /* The same, automatically: after every call on this context, device scratch beyond `bytes` is given back
  * (largest allocations first; 0, the default, keeps everything). For owners of many contexts - one
  * GridStream per field column - each of which would otherwise keep what its largest batch needed. A clone
- * (mdb_clone) starts with the limit of the context it was made from. */
+ * (mdb_clone) starts with the limit of the context it was made from.
+ * No call is refused for the limit, with one exception: mdb_comoments_buckets* fails when its y column alone
+ * (4 B per row under the time range) is larger than a limit other than 0, even where other operators take more
+ * transient scratch for the same batch. The caller then cuts the batch by series or lifts the limit for the call. */
 int mdb_set_scratch_limit(mdb_ctx *ctx, uint64_t bytes);
 /* Name, CU count, HBM bytes of the context's device. */
 int mdb_device_info(mdb_ctx *ctx, char *name, uint64_t name_cap, int32_t *compute_units,
@@ -510,6 +513,67 @@ int mdb_moments_merge_n(mdb_moments_cell *into, const mdb_moments_cell *from, ui
 /* Host arithmetic, no context, no GPU: variance_out[j] = m2 / (count - ddof) of cells[j]. ddof 0: var_pop (NaN for a
  * count of 0); ddof 1: var_samp (NaN for a count of 1 or less); any other ddof is an error. stddev is its sqrt. */
 int mdb_moments_variance(const mdb_moments_cell *cells, uint64_t n, uint32_t ddof, double *variance_out);
+
+/* Extension: covariance and correlation of two fields - per bucket of date_bin(width, ts, origin) and group the count,
+ * both means, both m2 and c_xy = the sum of (x - mean_x) * (y - mean_y) over the pairs of the bucket:
+ *   SELECT date_bin(...), corr(active_power, wind_speed), regr_slope(active_power, wind_speed) ... GROUP BY 1, turbine
+ * corr, covar_samp, covar_pop, regr_slope, regr_intercept and regr_r2 follow from a cell (mdb_comoments_finish). The
+ * reference answers them with GridExec per field -> SortedJoinExec -> AggregateExec: its model-based rule rewrites only
+ * count / min / max / sum / avg (crates/modelardb_storage/src/optimizer/model_simple_aggregates.rs:319-323), so every
+ * point of both fields is rebuilt and zipped by row position (query/sorted_join_exec.rs:278-310). Here x is walked on
+ * its segments and nothing of it is materialised; y is rebuilt values-only into a scratch column of 4 B per row that
+ * lives in HBM only and never crosses PCIe - the one thing the operator materialises.
+ *   x, y: two field columns of the same series with the same timestamps, each cut into segments in its own way (the
+ *     alignment rule of the row masks). x is the independent variable: the kinds below are SQL's regr_*(y, x).
+ *   request: mdb_bucket_request, unchanged; which_mask must be 0. inout: row-major [n_groups][n_buckets] cells
+ *     (mdb_comoments_cell, mdb_format.h); a fresh cell is all-zero bytes. group_of_segment_x: per segment of x, as for
+ *     mdb_agg_buckets.
+ *   Which points: the rows of mdb_grid_batch_range(x, t_lo, t_hi) and of mdb_grid_batch_range(y, t_lo, t_hi), in
+ *     order; row r of one is paired with row r of the other. A pair belongs to the bucket of its x-side timestamp and
+ *     the group of its x-side segment, and is counted exactly where mdb_agg_buckets counts the x point for the same
+ *     request: count equals that COUNT, always. Rows outside buckets 0 .. n_buckets-1 keep their place in the row
+ *     numbering and are not counted.
+ *   Alignment: only the row COUNT under [t_lo, t_hi] is checked; a mismatch fails before anything is written, with a
+ *     message that names both counts. The cuts of the lists xs and ys need not coincide.
+ *   How: a run of pairs (those of one x segment in one bucket) is accumulated around its first pair (Kx, Ky):
+ *     dx = (double)x - Kx, dy = (double)y - Ky, sx += dx, sy += dy, sxx += dx * dx, syy += dy * dy, sxy += dx * dy;
+ *     means and m2 as for mdb_moments_buckets, c_xy = sxy - sx * sy / n (not clamped).
+ *   Merge rule, the same in mdb_comoments_merge_n and in every kernel: means and m2 as mdb_moments_merge_n, and with
+ *     dx = mean_xb - mean_xa, dy likewise: c_xy = c_a + c_b + dx * dy * (na * nb / n); an empty side gives the other
+ *     side's bytes. A cell that receives no pair keeps every byte it had. A cell in which either field is constant has
+ *     c_xy == 0.0 exactly, in any order of merges; a pair of identical fields has m2_x, m2_y and c_xy of the same bytes.
+ *   Non-finite points: in a cell that holds a NaN or an infinity in a field count is exact, and that field's mean and
+ *     m2 and c_xy are not finite; nothing more is promised.
+ *   Determinism, as for mdb_moments_buckets: for the same input, request and form two runs agree bit for bit, and so
+ *     do the host, dev and list forms; no float atomics, no atomics on cells. MDB_AGG_BUCKET_SLICE_PAIRS, the order of
+ *     the segments and cutting a batch into calls move the f64 members by rounding only.
+ *   Scratch: the y column takes 4 B per row under [t_lo, t_hi]. Under mdb_set_scratch_limit a column larger than the
+ *     limit is refused with a message that states the bytes needed: cut the batch by series, the cells merge.
+ *   Errors (mdb_last_error set, inout untouched): those of mdb_moments_buckets*, a NULL y, the row-count mismatch, the
+ *     y column refused, a malformed segment in x or y. An empty batch or n_buckets == 0 succeeds and changes nothing. */
+#define MDB_COMOMENTS_COVAR_POP 0u      /* c / n;                        NaN when n = 0 */
+#define MDB_COMOMENTS_COVAR_SAMP 1u     /* c / (n - 1);                  NaN when n <= 1 */
+#define MDB_COMOMENTS_CORR 2u           /* c / sqrt(m2_x * m2_y);        NaN when n <= 1 or either m2 is 0 */
+#define MDB_COMOMENTS_REGR_SLOPE 3u     /* c / m2_x;                     NaN when n <= 1 or m2_x is 0 */
+#define MDB_COMOMENTS_REGR_INTERCEPT 4u /* mean_y - slope * mean_x;      as REGR_SLOPE */
+#define MDB_COMOMENTS_REGR_R2 5u        /* c * c / (m2_x * m2_y);        as CORR */
+int mdb_comoments_buckets(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, const uint32_t *group_of_segment_x,
+                          const mdb_bucket_request *request, mdb_comoments_cell *inout);
+/* All device pointers: both batches, group_of_segment_x and inout are in HBM. */
+int mdb_comoments_buckets_dev(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y,
+                              const uint32_t *group_of_segment_x, const mdb_bucket_request *request,
+                              mdb_comoments_cell *inout);
+/* Several host batches per field (rows in the order of each list) folded as one batch per field; group_of_segment_x:
+ * one array per batch of xs, or NULL. */
+int mdb_comoments_buckets_list(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys,
+                               uint32_t n_y, const uint32_t *const *group_of_segment_x,
+                               const mdb_bucket_request *request, mdb_comoments_cell *inout);
+/* Host arithmetic, no context, no GPU: into[j] merged with from[j] by the merge rule, for j < n. */
+int mdb_comoments_merge_n(mdb_comoments_cell *into, const mdb_comoments_cell *from, uint64_t n);
+/* Host arithmetic, no context, no GPU: out[j] = (count, mean, m2) of field `which` (0: x, 1: y) of cells[j]. */
+int mdb_comoments_moments(const mdb_comoments_cell *cells, uint64_t n, uint32_t which, mdb_moments_cell *out);
+/* Host arithmetic, no context, no GPU: out[j] = the MDB_COMOMENTS_* statistic `kind` of cells[j] (NaN as listed). */
+int mdb_comoments_finish(const mdb_comoments_cell *cells, uint64_t n, uint32_t kind, double *out);
 
 /* Extension: value histograms and exact quantiles PER BUCKET of date_bin(width, ts, origin) and group -
  *   SELECT date_bin(...), approx_percentile_cont(field, 0.95) ... GROUP BY 1 / median(field) per bucket / a heat map

@@ -218,6 +218,18 @@ typedef struct mdb_moments_cell {
     double  m2;
 } mdb_moments_cell;        /* 24 bytes */
 
+/* One cell of mdb_comoments_buckets*: the pairs (x, y) of a bucket and group - two fields of one table, paired row by
+ * row. (count, mean_x, m2_x) and (count, mean_y, m2_y) are the states of DataFusion's variance accumulators of either
+ * field, c_xy with the two means the state of its covariance accumulator: covar_pop / covar_samp, corr and regr_*
+ * follow (mdb_comoments_finish). A fresh cell is all-zero bytes. count == 0: the cell is empty and no other member is
+ * read; all are written when its first pairs arrive. */
+typedef struct mdb_comoments_cell {
+    int64_t count;
+    double  mean_x, mean_y;
+    double  m2_x, m2_y;   /* sum (x - mean_x)^2, sum (y - mean_y)^2 */
+    double  c_xy;         /* sum (x - mean_x) * (y - mean_y) */
+} mdb_comoments_cell;      /* 48 bytes */
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -319,5 +331,12 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_m4_cell, v_max) == 52);
 MDB_LAYOUT_ASSERT(sizeof(mdb_moments_cell) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_moments_cell, mean) == 8);
 MDB_LAYOUT_ASSERT(offsetof(mdb_moments_cell, m2) == 16);
+MDB_LAYOUT_ASSERT(sizeof(mdb_comoments_cell) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, count) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, mean_x) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, mean_y) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_x) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_y) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, c_xy) == 40);
 
 #endif /* MDB_FORMAT_H */

@@ -206,6 +206,19 @@ class MomentsCellC(C.Structure):
     ]
 
 
+class ComomentsCellC(C.Structure):
+    """mdb_comoments_cell: the count, both means, both m2 and c_xy = sum((x - mean_x) * (y - mean_y)) of the pairs of
+    one bucket and group (mdb_comoments_buckets*)."""
+    _fields_ = [
+        ("count", C.c_int64),
+        ("mean_x", C.c_double),
+        ("mean_y", C.c_double),
+        ("m2_x", C.c_double),
+        ("m2_y", C.c_double),
+        ("c_xy", C.c_double),
+    ]
+
+
 class HistRequestC(C.Structure):
     """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
     _fields_ = [
@@ -303,6 +316,16 @@ _HIP_SYMBOLS = {
                                            C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
     "mdb_moments_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_moments_variance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_comoments_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
+                                        C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_comoments_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
+                                            C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_comoments_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.c_uint32,
+                                             C.POINTER(C.POINTER(SegmentsC)), C.c_uint32, C.POINTER(C.c_void_p),
+                                             C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_comoments_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_comoments_moments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_comoments_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_grid_count_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC),
                                             C.POINTER(C.c_uint64)]),
     "mdb_grid_batch_filter_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(ValueFilterC), C.c_void_p,

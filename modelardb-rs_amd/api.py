@@ -204,6 +204,65 @@ def moments_variance(cells, ddof=1):
     return out.reshape(cells.shape)
 
 
+# mdb_comoments_cell as a numpy record: the cells of mdb_comoments_buckets*, row-major [n_groups][n_buckets].
+COMOMENTS_CELL_DTYPE = np.dtype([("count", "<i8"), ("mean_x", "<f8"), ("mean_y", "<f8"), ("m2_x", "<f8"),
+                                 ("m2_y", "<f8"), ("c_xy", "<f8")])
+assert COMOMENTS_CELL_DTYPE.itemsize == C.sizeof(_abi.ComomentsCellC)
+
+# The statistics of mdb_comoments_finish (MDB_COMOMENTS_*); x is the independent variable: SQL's regr_*(y, x).
+COMOMENTS_KINDS = {"covar_pop": 0, "covar_samp": 1, "corr": 2, "regr_slope": 3, "regr_intercept": 4, "regr_r2": 5}
+
+
+def fresh_comoments_cells(shape):
+    """Fresh (empty) comoments cells: all-zero bytes."""
+    return np.zeros(shape, dtype=COMOMENTS_CELL_DTYPE)
+
+
+def comoments_merge(into, from_):
+    """into[k] merged with from_[k] in place by the merge rule of mdb_comoments_buckets (mdb_comoments_merge_n): two
+    arrays of COMOMENTS_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != COMOMENTS_CELL_DTYPE or from_.dtype != COMOMENTS_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("comoments_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("comoments_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_comoments_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def comoments_moments(cells, which):
+    """The (count, mean, m2) of field `which` (0 or "x", 1 or "y") of every cell as MOMENTS_CELL_DTYPE
+    (mdb_comoments_moments): what moments_variance takes."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != COMOMENTS_CELL_DTYPE:
+        raise ValueError("comoments_moments takes an array of COMOMENTS_CELL_DTYPE")
+    which = {"x": 0, "y": 1}.get(which, which)
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = fresh_moments_cells(flat.size)
+    if lib.mdb_comoments_moments(flat.ctypes.data_as(C.c_void_p), flat.size, int(which),
+                                 out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
+def comoments_finish(cells, kind):
+    """The statistic `kind` (a name of COMOMENTS_KINDS or its number) per cell (mdb_comoments_finish): covar_pop,
+    covar_samp, corr, regr_slope, regr_intercept, regr_r2 - the regr_* with x as the independent variable; NaN where
+    the cell does not allow it. Returns float64 of the shape of `cells`."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != COMOMENTS_CELL_DTYPE:
+        raise ValueError("comoments_finish takes an array of COMOMENTS_CELL_DTYPE")
+    kind = COMOMENTS_KINDS.get(kind, kind)
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if lib.mdb_comoments_finish(flat.ctypes.data_as(C.c_void_p), flat.size, int(kind),
+                                out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -381,7 +440,8 @@ class Context:
         return released.value
 
     def set_scratch_limit(self, nbytes):
-        """Device scratch beyond `nbytes` is given back after every call (0: keep everything)."""
+        """Device scratch beyond `nbytes` is given back after every call (0: keep everything). Only comoments_buckets*
+        is refused for it: when its y column alone (4 B per row) is larger."""
         self._check(self.lib.mdb_set_scratch_limit(self.handle, C.c_uint64(nbytes)))
 
     # ---- device memory -----------------------------------------------------------------------
@@ -1047,6 +1107,90 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the data inside the range spans more than one bucket can hold: use moments_buckets")
         return self.moments_buckets(batch, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
+
+    # ---- covariance and correlation of two fields: count, means, m2 and c_xy per time bucket ----------
+
+    @staticmethod
+    def _comoments_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_comoments_cells((n_groups, n_buckets))
+        if cells.dtype != COMOMENTS_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of COMOMENTS_CELL_DTYPE")
+        return cells
+
+    def comoments_buckets(self, x, y, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                          n_groups=None):
+        """The count, both means, both m2 and c_xy of the pairs (x, y) per bucket of date_bin(width, ts, origin) and
+        group (mdb_comoments_buckets): x and y are two field batches of the same series that line up row for row.
+        Returns `cells` (or fresh ones), shape (n_groups, n_buckets), merged in place. `groups` (per segment of x) and
+        n_groups as for agg_buckets; comoments_finish turns cells into corr / covar_* / regr_*. `x is y` is uploaded
+        once."""
+        groups = self._groups_array(groups, len(x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._comoments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        x_view = x.as_c()
+        y_view = x_view if y is x else y.as_c()
+        self._check(self.lib.mdb_comoments_buckets(self.handle, C.byref(x_view), C.byref(y_view),
+                                                   None if groups is None else groups.ctypes.data_as(C.c_void_p),
+                                                   C.byref(request), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def comoments_buckets_list(self, xs, ys, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                               n_groups=None):
+        """Several host batches per field merged as one (mdb_comoments_buckets_list): the cuts of xs and ys need not
+        coincide; `groups`: None or one array (or None) per batch of xs."""
+        batch_groups = [None] * len(xs) if groups is None else [self._groups_array(g, len(b))
+                                                                for g, b in zip(groups, xs)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._comoments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        x_views = [batch.as_c() for batch in xs]
+        y_views = [batch.as_c() for batch in ys]
+        x_pointers = (C.POINTER(_abi.SegmentsC) * max(len(x_views), 1))(*[C.pointer(view) for view in x_views])
+        y_pointers = (C.POINTER(_abi.SegmentsC) * max(len(y_views), 1))(*[C.pointer(view) for view in y_views])
+        group_pointers = (C.c_void_p * max(len(x_views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_comoments_buckets_list(self.handle, x_pointers, len(x_views), y_pointers, len(y_views),
+                                                        group_pointers, C.byref(request),
+                                                        cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def comoments_buckets_dev(self, dev_x, dev_y, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                              cells=None, n_groups=None):
+        """mdb_comoments_buckets_dev on two resident batches: `groups` and `cells` are uploaded, the cells downloaded
+        again."""
+        groups = self._groups_array(groups, len(dev_x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._comoments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_comoments_buckets_dev(self.handle, C.byref(dev_x.seg), C.byref(dev_y.seg),
+                                                           None if dev_groups is None else C.c_void_p(dev_groups),
+                                                           C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, COMOMENTS_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def comoments(self, x, y, t_lo=None, t_hi=None, groups=None, n_groups=None):
+        """The cells of the pairs of `x` and `y` inside [t_lo, t_hi], one per group (shape (n_groups,)): one bucket
+        over the data inside the range, what a whole-batch corr / covar / regr query needs."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(x))])
+        if len(x) == 0:
+            return fresh_comoments_cells(n_groups)
+        lo, hi = int(np.min(x.start_time)), int(np.max(x.end_time))
+        lo = lo if t_lo is None else max(lo, int(t_lo))
+        hi = hi if t_hi is None else min(hi, int(t_hi))
+        if lo > hi:
+            return fresh_comoments_cells(n_groups)
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the data inside the range spans more than one bucket can hold: use comoments_buckets")
+        return self.comoments_buckets(x, y, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
 
     @staticmethod
     def _n_groups(n_groups, states, groups):

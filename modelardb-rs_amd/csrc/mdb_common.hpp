@@ -97,6 +97,8 @@ enum ScratchSlot {
     SCRATCH_HIST_CELLS,      // mdb_hist_* / mdb_quantile_*: the zeroed cells of one pass, the edges' keys, the error word
     SCRATCH_HIST_BUCKET_OFFSETS, // mdb_hist_buckets* / mdb_quantile_buckets*: slot offsets per segment and their scan
     SCRATCH_HIST_BUCKET_SLOTS,   // ... the index interval per (segment, bucket) of irregular timestamps under a bit stream
+    SCRATCH_COMOMENTS_ROWS,      // mdb_comoments_buckets*: rows and first rows of the x field's segments, the scan's sums
+    SCRATCH_COMOMENTS_YCOL,      // ... the y column: one f32 per row of the y field under the time range
     SCRATCH_SLOT_COUNT
 };
 

@@ -33,7 +33,8 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
-    mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell, mdb_moments_cell as MomentsCell,
+    mdb_comoments_cell as ComomentsCell, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
+    mdb_moments_cell as MomentsCell,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
@@ -357,6 +358,32 @@ pub fn moments_merge(into: &mut [MomentsCell], from: &[MomentsCell]) -> Result<(
         return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
     }
     check(unsafe { sys::mdb_moments_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// `into[j]` merged with `from[j]` by the merge rule of [`Context::comoments_buckets`] (host arithmetic, no GPU): what
+/// a `CovarianceAccumulator`-shaped accumulator does in `merge_batch`.
+pub fn comoments_merge(into: &mut [ComomentsCell], from: &[ComomentsCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_comoments_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The `(count, mean, m2)` of the x field (`which` 0) or the y field (1) of every cell: what [`moments_variance`]
+/// takes (host arithmetic, no GPU).
+pub fn comoments_moments(cells: &[ComomentsCell], which: u32) -> Result<Vec<MomentsCell>> {
+    let mut out = vec![MomentsCell::default(); cells.len()];
+    check(unsafe { sys::mdb_comoments_moments(cells.as_ptr(), cells.len() as u64, which, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The statistic `kind` (`sys::MDB_COMOMENTS_*`) per cell (host arithmetic, no GPU): `covar_pop`, `covar_samp`,
+/// `corr`, `regr_slope`, `regr_intercept`, `regr_r2` - the `regr_*` with x as the independent variable, SQL's
+/// `regr_*(y, x)`; NaN where the cell does not allow it.
+pub fn comoments_finish(cells: &[ComomentsCell], kind: u32) -> Result<Vec<f64>> {
+    let mut out = vec![0.0f64; cells.len()];
+    check(unsafe { sys::mdb_comoments_finish(cells.as_ptr(), cells.len() as u64, kind, out.as_mut_ptr()) })?;
+    Ok(out)
 }
 
 /// `m2 / (count - ddof)` per cell (host arithmetic, no GPU): `ddof` 0 is `var_pop`, 1 `var_samp`; NaN where the count
@@ -763,6 +790,58 @@ impl Context {
         check(unsafe {
             sys::mdb_moments_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                           request, cells.as_mut_ptr())
+        })
+    }
+
+    /// Covariance and correlation of two fields: per bucket of `date_bin(width, ts, origin)` and group the count, both
+    /// means, both `m2` and `c_xy` of the pairs `(x, y)`. `x` and `y` are two field columns of the same series that
+    /// line up row for row under the request's time range (only the row count is checked); `x` is walked on its
+    /// segments, `y` is rebuilt values-only into device scratch (4 B per row, never copied to the host). `cells` is
+    /// row-major `[n_groups][n_buckets]` (fresh: `ComomentsCell::default()`); the batches are merged into it, and a
+    /// cell without pairs stays as it was. `group_of_segment_x` is per segment of `x`; `request.which_mask` must be 0.
+    /// [`comoments_finish`] turns cells into `corr` / `covar_*` / `regr_*`.
+    pub fn comoments_buckets(
+        &self,
+        x: &SegmentsView,
+        y: &SegmentsView,
+        group_of_segment_x: Option<&[u32]>,
+        request: &BucketRequest,
+        cells: &mut [ComomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        check_group_ids(x, group_of_segment_x)?;
+        let groups = group_of_segment_x.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_comoments_buckets(self.raw(), &x.raw, &y.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::comoments_buckets`] for several batches per field (rows in the order of each slice), merged as one
+    /// batch per field: the cuts of `xs` and `ys` need not coincide. `group_of_segment_x`: `None`, or one entry per
+    /// batch of `xs` (`None`: that batch's rows in group 0).
+    pub fn comoments_buckets_list(
+        &self,
+        xs: &[SegmentsView],
+        ys: &[SegmentsView],
+        group_of_segment_x: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        cells: &mut [ComomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        if let Some(groups) = group_of_segment_x {
+            if groups.len() != xs.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), xs.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(xs.len());
+        for (k, view) in xs.iter().enumerate() {
+            let groups = group_of_segment_x.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let x_inputs: Vec<*const sys::mdb_segments> = xs.iter().map(|view| &view.raw as *const _).collect();
+        let y_inputs: Vec<*const sys::mdb_segments> = ys.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_comoments_buckets_list(self.raw(), x_inputs.as_ptr(), x_inputs.len() as u32, y_inputs.as_ptr(),
+                                            y_inputs.len() as u32, group_pointers.as_ptr(), request, cells.as_mut_ptr())
         })
     }
 

@@ -253,6 +253,29 @@ pub struct mdb_m4_cell {
     pub v_max: f32,
 }
 
+/// One cell of `mdb_comoments_buckets*`: the pairs `(x, y)` of a bucket and group. `(count, mean_x, m2_x)` and
+/// `(count, mean_y, m2_y)` are the states of DataFusion's variance accumulators of either field, `c_xy` (the sum of
+/// `(x - mean_x) * (y - mean_y)`) with the two means the state of its covariance accumulator. A fresh cell is all-zero
+/// bytes (`Default`); `count == 0`: empty, no other member is read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_comoments_cell {
+    pub count: i64,
+    pub mean_x: f64,
+    pub mean_y: f64,
+    pub m2_x: f64,
+    pub m2_y: f64,
+    pub c_xy: f64,
+}
+
+/// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
+pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
+pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
+pub const MDB_COMOMENTS_CORR: u32 = 2;
+pub const MDB_COMOMENTS_REGR_SLOPE: u32 = 3;
+pub const MDB_COMOMENTS_REGR_INTERCEPT: u32 = 4;
+pub const MDB_COMOMENTS_REGR_R2: u32 = 5;
+
 /// One cell of `mdb_moments_buckets*`: the count, the mean and `m2`, the sum of `(v - mean)^2`, of a bucket and group:
 /// the state of DataFusion's variance accumulators. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty,
 /// no other member is read.
@@ -412,6 +435,19 @@ unsafe extern "C" {
                                     request: *const mdb_bucket_request, inout: *mut mdb_moments_cell) -> c_int;
     pub fn mdb_moments_merge_n(into: *mut mdb_moments_cell, from: *const mdb_moments_cell, n: u64) -> c_int;
     pub fn mdb_moments_variance(cells: *const mdb_moments_cell, n: u64, ddof: u32, variance_out: *mut f64) -> c_int;
+    pub fn mdb_comoments_buckets(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                                 group_of_segment_x: *const u32, request: *const mdb_bucket_request,
+                                 inout: *mut mdb_comoments_cell) -> c_int;
+    pub fn mdb_comoments_buckets_dev(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                                     group_of_segment_x: *const u32, request: *const mdb_bucket_request,
+                                     inout: *mut mdb_comoments_cell) -> c_int;
+    pub fn mdb_comoments_buckets_list(ctx: *mut mdb_ctx, xs: *const *const mdb_segments, n_x: u32,
+                                      ys: *const *const mdb_segments, n_y: u32,
+                                      group_of_segment_x: *const *const u32, request: *const mdb_bucket_request,
+                                      inout: *mut mdb_comoments_cell) -> c_int;
+    pub fn mdb_comoments_merge_n(into: *mut mdb_comoments_cell, from: *const mdb_comoments_cell, n: u64) -> c_int;
+    pub fn mdb_comoments_moments(cells: *const mdb_comoments_cell, n: u64, which: u32, out: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_comoments_finish(cells: *const mdb_comoments_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
     pub fn mdb_quantile_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
                               n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
@@ -558,3 +594,10 @@ const _: () = assert!(offset_of!(mdb_m4_cell, v_max) == 52);
 const _: () = assert!(size_of::<mdb_moments_cell>() == 24);
 const _: () = assert!(offset_of!(mdb_moments_cell, mean) == 8);
 const _: () = assert!(offset_of!(mdb_moments_cell, m2) == 16);
+const _: () = assert!(size_of::<mdb_comoments_cell>() == 48);
+const _: () = assert!(offset_of!(mdb_comoments_cell, count) == 0);
+const _: () = assert!(offset_of!(mdb_comoments_cell, mean_x) == 8);
+const _: () = assert!(offset_of!(mdb_comoments_cell, mean_y) == 16);
+const _: () = assert!(offset_of!(mdb_comoments_cell, m2_x) == 24);
+const _: () = assert!(offset_of!(mdb_comoments_cell, m2_y) == 32);
+const _: () = assert!(offset_of!(mdb_comoments_cell, c_xy) == 40);
