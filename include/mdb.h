@@ -640,6 +640,67 @@ int mdb_quantile_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_
                              const mdb_bucket_request *request, const double *q, uint32_t n_q, float *out_lo,
                              float *out_hi, uint64_t *n_points);
 
+/* Extension: the moments of one field per VALUE CELL of another - per bucket of date_bin(width, ts, origin), group and
+ * cell of x the count, the mean and m2 = the sum of (y - mean)^2 of the y values of the pairs whose x value falls in
+ * the cell:
+ *   SELECT width_bucket(wind_speed, ...), count(active_power), avg(active_power), stddev(active_power) ...
+ *     GROUP BY 1 [, date_bin(...), turbine]
+ * - the power curve of IEC 61400-12 (the "method of bins"), efficiency against load, a scatter plot reduced to a band.
+ * The reference answers it with GridExec per field -> SortedJoinExec -> AggregateExec, every point of both fields
+ * rebuilt. Here x is walked on its segments and contributes only the boundaries of its runs; y is the values-only
+ * column of mdb_comoments_buckets (4 B per row, HBM only).
+ *   Pairs: exactly those of mdb_comoments_buckets - row r of mdb_grid_batch_range(x, t_lo, t_hi) with row r of the same
+ *     for y; a pair takes the bucket of its x-side timestamp and the group of its x-side segment. Rows outside buckets
+ *     0 .. n_buckets-1 keep their row number and are not counted. Only the row COUNT under [t_lo, t_hi] is checked; a
+ *     mismatch fails before anything is written, with a message that names both counts. The cuts of x and y need not
+ *     coincide.
+ *   Cell: that of mdb_hist_cell_of applied to the x value - 1 .. MDB_HIST_MAX_EDGES edges, strictly increasing in
+ *     totalOrder, n_cells = n_edges + 1, the cell = the number of edges at or below the value's key. A NaN, a +-0 or an
+ *     infinity of x lands where its key puts it.
+ *   inout: mdb_moments_cell, row-major [n_groups][n_buckets][n_cells]; a fresh cell is all-zero bytes. A call MERGES
+ *     into it; a cell that receives no pair keeps every byte it had. mdb_moments_merge_n and mdb_moments_variance take
+ *     the cells unchanged. which_mask must be 0.
+ *   How: a run is a maximal stretch of consecutive pairs of one x segment that stay in one bucket and one cell. It is
+ *     summed around its first y value K: d = (double)y - (double)K, s1 += d, s2 += d * d; mean = K + s1 / n,
+ *     m2 = s2 - s1 * s1 / n (0 where that rounds below 0). Runs meet only through the merge rule of
+ *     mdb_moments_merge_n: a cell whose y values are all equal has m2 == 0.0 and mean == the value exactly, in any order
+ *     of merges. PMC-Mean on regular timestamps is one run per bucket reached; Swing on regular timestamps the binary
+ *     searches of mdb_hist_batch per bucket; a stream of values or timestamps is decoded a constant number of times
+ *     per pass (two passes: one counts the runs, one reduces y over them), as mdb_hist_buckets does; only a malformed
+ *     stream whose timestamps are not sorted is walked bucket by bucket. The batch's cursor index is not used.
+ *   Invariants: count[g][b][c] equals what mdb_hist_buckets(x, the same request, the same edges) adds, exactly and
+ *     always; its sum over c equals the COUNT of mdb_agg_buckets(x); the cells of a (group, bucket) folded over c with
+ *     mdb_moments_merge_n give, within the moments' tolerance, the y moments of mdb_comoments_buckets(x, y).
+ *   Non-finite y: in a cell that holds a NaN or an infinity of y count is exact and neither mean nor m2 is finite;
+ *     nothing more is promised. A non-finite x only decides the cell.
+ *   Determinism, as for mdb_moments_buckets: for the same input, request, edges and form two runs agree bit for bit,
+ *     and so do the host, dev and list forms; no float atomics, no atomics on cells. MDB_AGG_BUCKET_SLICE_PAIRS, the
+ *     order of the segments, cutting a batch into calls and whether the keys had to be sorted move mean and m2 by
+ *     rounding only.
+ *   Scratch: the y column takes 4 B per row under [t_lo, t_hi] (refused under mdb_set_scratch_limit as for
+ *     mdb_comoments_buckets); a run takes 32 B, the cell and its 8-byte key; 16 B per segment of x for the run counts
+ *     and offsets, which are also read back once (8 B per segment) to cut the slices. On an x field whose noise crosses
+ *     an edge at every point runs approach points. Slices of at most MDB_AGG_BUCKET_SLICE_PAIRS runs are folded one
+ *     after the other; a slice ends only at a segment boundary, so a single segment with more runs than that is a slice
+ *     of its own and needs 32 B for each of its runs (at most 2^31 runs in one segment).
+ *   Errors (mdb_last_error set, inout untouched): those of mdb_comoments_buckets* - a NULL argument, a NULL y, the
+ *     row-count mismatch, the y column refused, a malformed segment in x or y - and those of mdb_hist_buckets*: a bad
+ *     edge list, n_groups * n_buckets * n_cells overflowing or not fitting the device's memory, a group id >= n_groups
+ *     on ANY row. What can be checked without the device is checked before it is used. An empty batch, n_buckets == 0
+ *     or an empty time range succeeds and changes nothing. */
+int mdb_binned_buckets(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, const uint32_t *group_of_segment_x,
+                       const mdb_bucket_request *request, const float *edges, uint32_t n_edges, mdb_moments_cell *inout);
+/* Both batches, group_of_segment_x and inout are in HBM; request and edges are host pointers. */
+int mdb_binned_buckets_dev(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y,
+                           const uint32_t *group_of_segment_x, const mdb_bucket_request *request, const float *edges,
+                           uint32_t n_edges, mdb_moments_cell *inout);
+/* Several host batches per field (rows in the order of each list) folded as one batch per field; group_of_segment_x:
+ * one array per batch of xs, or NULL. */
+int mdb_binned_buckets_list(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys,
+                            uint32_t n_y, const uint32_t *const *group_of_segment_x,
+                            const mdb_bucket_request *request, const float *edges, uint32_t n_edges,
+                            mdb_moments_cell *inout);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

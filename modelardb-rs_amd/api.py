@@ -1192,6 +1192,98 @@ class Context:
             raise ValueError("the data inside the range spans more than one bucket can hold: use comoments_buckets")
         return self.comoments_buckets(x, y, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
 
+    # ---- moments of one field per value cell of another: count, mean and m2 of y per cell of x ----------
+
+    @staticmethod
+    def _binned_cells(cells, n_groups, n_buckets, n_cells):
+        if cells is None:
+            return fresh_moments_cells((n_groups, n_buckets, n_cells))
+        if (cells.dtype != MOMENTS_CELL_DTYPE or cells.shape != (n_groups, n_buckets, n_cells)
+                or not cells.flags.c_contiguous):
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}, {n_cells}) array of MOMENTS_CELL_DTYPE")
+        return cells
+
+    def binned_buckets(self, x, y, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                       n_groups=None):
+        """The count, mean and m2 of the y values per bucket of date_bin(width, ts, origin), group and value cell of x
+        (mdb_binned_buckets): x and y are two field batches of the same series that line up row for row, the cell of
+        a pair is hist_cell_of(edges, its x value). Returns `cells` (or fresh ones), MOMENTS_CELL_DTYPE of shape
+        (n_groups, n_buckets, len(edges) + 1), merged in place: moments_merge and moments_variance apply. `groups` (per
+        segment of x) and n_groups as for agg_buckets. `x is y` is uploaded once."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._binned_cells(cells, n_groups, n_buckets, len(edges) + 1)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        x_view = x.as_c()
+        y_view = x_view if y is x else y.as_c()
+        self._check(self.lib.mdb_binned_buckets(self.handle, C.byref(x_view), C.byref(y_view),
+                                                None if groups is None else groups.ctypes.data_as(C.c_void_p),
+                                                C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def binned_buckets_list(self, xs, ys, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                            cells=None, n_groups=None):
+        """Several host batches per field merged as one (mdb_binned_buckets_list): the cuts of xs and ys need not
+        coincide; `groups`: None or one array (or None) per batch of xs."""
+        edges = _edges_array(edges)
+        batch_groups = [None] * len(xs) if groups is None else [self._groups_array(g, len(b))
+                                                                for g, b in zip(groups, xs)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._binned_cells(cells, n_groups, n_buckets, len(edges) + 1)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        x_views = [batch.as_c() for batch in xs]
+        y_views = [batch.as_c() for batch in ys]
+        x_pointers = (C.POINTER(_abi.SegmentsC) * max(len(x_views), 1))(*[C.pointer(view) for view in x_views])
+        y_pointers = (C.POINTER(_abi.SegmentsC) * max(len(y_views), 1))(*[C.pointer(view) for view in y_views])
+        group_pointers = (C.c_void_p * max(len(x_views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_binned_buckets_list(self.handle, x_pointers, len(x_views), y_pointers, len(y_views),
+                                                     group_pointers, C.byref(request),
+                                                     edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                     cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def binned_buckets_dev(self, dev_x, dev_y, edges, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                           cells=None, n_groups=None):
+        """mdb_binned_buckets_dev on two resident batches: `groups` and `cells` are uploaded, the cells downloaded
+        again."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(dev_x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._binned_cells(cells, n_groups, n_buckets, len(edges) + 1)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_binned_buckets_dev(self.handle, C.byref(dev_x.seg), C.byref(dev_y.seg),
+                                                        None if dev_groups is None else C.c_void_p(dev_groups),
+                                                        C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                        C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, MOMENTS_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def binned(self, x, y, edges, t_lo=None, t_hi=None, groups=None, n_groups=None):
+        """The cells of the pairs of `x` and `y` inside [t_lo, t_hi] per group and value cell of x, shape
+        (n_groups, len(edges) + 1): one bucket over the data inside the range - the power curve."""
+        n_cells = len(_edges_array(edges)) + 1
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(x))])
+        if len(x) == 0:
+            return fresh_moments_cells((n_groups, n_cells))
+        lo, hi = int(np.min(x.start_time)), int(np.max(x.end_time))
+        lo = lo if t_lo is None else max(lo, int(t_lo))
+        hi = hi if t_hi is None else min(hi, int(t_hi))
+        if lo > hi:
+            return fresh_moments_cells((n_groups, n_cells))
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the data inside the range spans more than one bucket can hold: use binned_buckets")
+        return self.binned_buckets(x, y, edges, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups, n_cells)
+
     @staticmethod
     def _n_groups(n_groups, states, groups):
         if n_groups is not None:

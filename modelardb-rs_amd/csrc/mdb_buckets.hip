@@ -208,7 +208,9 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_partials(DevSegme
 __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_check(const unsigned long long *__restrict__ keys,
                                                                      uint64_t n, unsigned int *__restrict__ unsorted) {
     const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x + 1;
-    if (j < n && keys[j] < keys[j - 1]) atomicOr(unsorted, 1u);
+    // (the flag is read first: keys that descend everywhere - the runs of mdb_binned_buckets* - then cost the few
+    // atomics of the waves that run before the first one lands, not one per wave)
+    if (j < n && keys[j] < keys[j - 1] && *(volatile const unsigned int *)unsorted == 0) atomicOr(unsorted, 1u);
 }
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_iota(uint32_t *__restrict__ out, uint64_t n) {

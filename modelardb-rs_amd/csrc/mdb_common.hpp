@@ -99,6 +99,7 @@ enum ScratchSlot {
     SCRATCH_HIST_BUCKET_SLOTS,   // ... the index interval per (segment, bucket) of irregular timestamps under a bit stream
     SCRATCH_COMOMENTS_ROWS,      // mdb_comoments_buckets*: rows and first rows of the x field's segments, the scan's sums
     SCRATCH_COMOMENTS_YCOL,      // ... the y column: one f32 per row of the y field under the time range
+    SCRATCH_BINNED,              // mdb_binned_buckets*: run counts and offsets per x segment, the scan's sums, the edges' keys
     SCRATCH_SLOT_COUNT
 };
 

@@ -223,8 +223,8 @@ __global__ __launch_bounds__(MDB_WAVE) void k_comoments_pieces(
 
 // The rows of x and y under [t_lo, t_hi] compared, x's first rows (n + 1, in SCRATCH_COMOMENTS_ROWS: a slot of its
 // own, the range grid of y and the row masks use theirs meanwhile) and the y column (SCRATCH_COMOMENTS_YCOL).
-static int comoments_rows(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, int64_t t_lo, int64_t t_hi,
-                          const unsigned long long **first_row, YColumn *column) {
+int comoments_rows(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, int64_t t_lo, int64_t t_hi,
+                   const unsigned long long **first_row, YColumn *column) {
     const uint64_t n = x->n;
     if (n > 0xffffffffull) return fail("Too many segments for one call of mdb_comoments_buckets*.");
     const uint64_t b4 = align_up(n * 4, 256), b8 = align_up((n + 1) * 8, 256);

@@ -142,6 +142,12 @@ struct YColumn {
     }
 };
 
+// mdb_comoments.hip (mdb_binned.hip too): the rows of x and y under [t_lo, t_hi] compared - a mismatch fails with both
+// counts - x's first rows (n + 1 of them, SCRATCH_COMOMENTS_ROWS) and the y column (SCRATCH_COMOMENTS_YCOL). Both slots
+// are filled anew by every call that reads them, under the context's lock.
+int comoments_rows(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, int64_t t_lo, int64_t t_hi,
+                   const unsigned long long **first_row, YColumn *column);
+
 // The model points [a, b] of a PMC-Mean or Swing segment with regular timestamps as one run, point by point in
 // registers on the x side (as moments_model_points does for Swing), one read of the y column per point: there is no
 // O(1) case, not for PMC-Mean either - the y side needs every row.

@@ -44,23 +44,6 @@ namespace mdb {
 
 static_assert(SELECT_PASSES == MDB_QUANTILE_BUCKETS_PASSES, "mdb.h states the passes of the selection");
 
-// Does segment i keep per-bucket index intervals in slots? Irregular timestamps and values in a bit stream, judged by
-// the views alone (a superset of what analyse_segment finds: a residual view that holds no point still gets slots).
-__device__ __forceinline__ bool hist_bucket_wants_slots(const DevSegments &s, uint64_t i) {
-    if (segment_has_regular_timestamps(s, i) || (int32_t)s.timestamps.views[i].x <= 0) return false;
-    return s.model_type_id[i] == MDB_MACAQUE_V_ID || (int32_t)s.residuals.views[i].x > 0;
-}
-
-struct HistSlotCount { // the functor of the scan
-    DevSegments s;
-    BucketRequest r;
-    __device__ uint64_t operator()(uint64_t i) const {
-        if (!hist_bucket_wants_slots(s, i)) return 0;
-        uint64_t first = 0;
-        return bucket_span(s.start_time[i], s.end_time[i], r, &first);
-    }
-};
-
 // The two cell rules of k_hist_buckets: what the kernel is given, and the lane it makes of it.
 struct EdgeRule {
     using Lane = HistLane;
@@ -349,25 +332,6 @@ __global__ __launch_bounds__(HIST_THREADS) void k_quantile_select(const unsigned
     remaining[lane] = left;
 }
 
-namespace {
-
-// The checks on a request every form makes before it touches the device: those of mdb_m4_buckets*; *n_rows =
-// n_groups * n_buckets, with row_cells counters each.
-int hist_buckets_request_check(const mdb_bucket_request *request, uint64_t row_cells, const char *what, uint64_t *n_rows) {
-    if (request->which_mask != 0) return fail(std::string("which_mask must be 0 for ") + what + ".");
-    if (request->width <= 0) return fail("The bucket width must be positive.");
-    if (request->n_groups == 0) return fail("n_groups must be at least 1.");
-    const unsigned __int128 rows = (unsigned __int128)request->n_groups * request->n_buckets;
-    if (rows * row_cells > (unsigned __int128)(UINT64_MAX / 16)) return fail("n_groups * n_buckets * n_cells overflows.");
-    *n_rows = (uint64_t)rows;
-    return 0;
-}
-
-BucketRequest bucket_request_of(const mdb_bucket_request *request) {
-    return BucketRequest{request->origin, request->width, request->n_buckets, request->t_lo, request->t_hi,
-                         request->n_groups, request->which_mask};
-}
-
 // Counters (and slots) that cannot fit the device are an error, asked only where it could matter.
 int hist_buckets_fits(uint64_t bytes, const char *what) {
     if (bytes <= (1ull << 30)) return 0;
@@ -377,11 +341,6 @@ int hist_buckets_fits(uint64_t bytes, const char *what) {
         return fail(std::string(what) + " (" + std::to_string(bytes) + " bytes) do not fit into the device's memory.");
     return 0;
 }
-
-struct HistSlots { // the slots of the segments with irregular timestamps under bit-stream values
-    const unsigned long long *offsets = nullptr;
-    uint2 *slots = nullptr;
-};
 
 // k_hist_bucket_slots' scan and the slots themselves (SCRATCH_HIST_BUCKET_SLOTS).
 int hist_buckets_slots(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const BucketRequest &r, HistSlots *out) {
@@ -404,6 +363,25 @@ int hist_buckets_slots(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &
     if (scratch_reserve(ctx, SCRATCH_HIST_BUCKET_SLOTS, total * 8, &p)) return 1;
     out->slots = static_cast<uint2 *>(p);
     return 0;
+}
+
+namespace {
+
+// The checks on a request every form makes before it touches the device: those of mdb_m4_buckets*; *n_rows =
+// n_groups * n_buckets, with row_cells counters each.
+int hist_buckets_request_check(const mdb_bucket_request *request, uint64_t row_cells, const char *what, uint64_t *n_rows) {
+    if (request->which_mask != 0) return fail(std::string("which_mask must be 0 for ") + what + ".");
+    if (request->width <= 0) return fail("The bucket width must be positive.");
+    if (request->n_groups == 0) return fail("n_groups must be at least 1.");
+    const unsigned __int128 rows = (unsigned __int128)request->n_groups * request->n_buckets;
+    if (rows * row_cells > (unsigned __int128)(UINT64_MAX / 16)) return fail("n_groups * n_buckets * n_cells overflows.");
+    *n_rows = (uint64_t)rows;
+    return 0;
+}
+
+BucketRequest bucket_request_of(const mdb_bucket_request *request) {
+    return BucketRequest{request->origin, request->width, request->n_buckets, request->t_lo, request->t_hi,
+                         request->n_groups, request->which_mask};
 }
 
 template <typename Rule>

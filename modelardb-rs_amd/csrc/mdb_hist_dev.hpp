@@ -147,6 +147,33 @@ struct HistCellsOf {
 };
 using HistCells = HistCellsOf<HistLane>;
 
+// Does segment i keep per-bucket index intervals in slots? Irregular timestamps and values in a bit stream, judged by
+// the views alone (a superset of what analyse_segment finds: a residual view that holds no point still gets slots).
+__device__ __forceinline__ bool hist_bucket_wants_slots(const DevSegments &s, uint64_t i) {
+    if (segment_has_regular_timestamps(s, i) || (int32_t)s.timestamps.views[i].x <= 0) return false;
+    return s.model_type_id[i] == MDB_MACAQUE_V_ID || (int32_t)s.residuals.views[i].x > 0;
+}
+
+struct HistSlotCount { // the functor of the scan
+    DevSegments s;
+    BucketRequest r;
+    __device__ uint64_t operator()(uint64_t i) const {
+        if (!hist_bucket_wants_slots(s, i)) return 0;
+        uint64_t first = 0;
+        return bucket_span(s.start_time[i], s.end_time[i], r, &first);
+    }
+};
+
+struct HistSlots { // the slots of the segments with irregular timestamps under bit-stream values
+    const unsigned long long *offsets = nullptr;
+    uint2 *slots = nullptr;
+};
+
+// mdb_hist_buckets.hip (mdb_binned.hip too): counters or slots that cannot fit the device are an error, asked only where
+// it could matter; k_hist_bucket_slots' scan and the slots themselves (SCRATCH_HIST_BUCKET_OFFSETS / _SLOTS).
+int hist_buckets_fits(uint64_t bytes, const char *what);
+int hist_buckets_slots(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const BucketRequest &r, HistSlots *out);
+
 // mdb_hist.hip, for the callers of mdb_hist_buckets.hip: k_hist_groups over the n ids of `groups` (sets ERR_HIST_GROUP in
 // *error), and k_hist_fold (counts[j] += cells[j] where cells[j] != 0), both enqueued on the context's stream.
 void hist_groups_launch(mdb_ctx *ctx, const uint32_t *groups, uint64_t n, uint32_t n_groups, unsigned int *error);

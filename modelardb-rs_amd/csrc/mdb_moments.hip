@@ -204,6 +204,55 @@ __global__ __launch_bounds__(MDB_WAVE) void k_moments_pieces(DevSegments s, Buck
     if (to_decode > 0) flush(); // (bucket == b_last)
 }
 
+int moments_tree_reserve(mdb_ctx *ctx, uint64_t cap, MomentsTreeScratch *out) {
+    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
+    uint64_t tree_entries = 0;
+    for (uint64_t m = cap; m > BUCKET_TILE;) {
+        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
+        tree_entries += m + 1;
+    }
+    void *p;
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_moments_cell)) + 256, &p)) return 1;
+    out->values = static_cast<mdb_moments_cell *>(p);
+    out->keys = reinterpret_cast<unsigned long long *>(out->values + tree_entries);
+    return 0;
+}
+
+int moments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_moments_cell *partials, uint64_t m, bool unsorted,
+                       unsigned int key_bits, const MomentsTreeScratch &scratch, mdb_moments_cell *cells) {
+    MomentsTree tree = {};
+    tree.keys[0] = keys;
+    tree.values[0] = partials;
+    tree.n[0] = m;
+    tree.order = nullptr;
+    if (unsorted) { // keys out of order: a stable sort by key, pair numbers alongside
+        if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
+    }
+    // The tree's levels over this slice, then the fold.
+    tree.levels = 1;
+    uint64_t used = 0;
+    {
+        LaunchTimer timer(ctx, "k_moments_tree");
+        for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
+            const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
+            unsigned long long *level_keys = scratch.keys + used;
+            mdb_moments_cell *level_values = scratch.values + used;
+            hipLaunchKernelGGL(k_moments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
+                               tree.levels - 1, level_keys, level_values);
+            tree.keys[tree.levels] = level_keys;
+            tree.values[tree.levels] = level_values;
+            tree.n[tree.levels] = up;
+            used += up + 1;
+            size = up;
+        }
+    }
+    {
+        LaunchTimer timer(ctx, "k_moments_fold");
+        hipLaunchKernelGGL(k_moments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
+    }
+    return 0;
+}
+
 // The buckets of the device batch `in` (groups: a device array or nullptr) merged into a device array of n_cells
 // cells. `host_cells` (host forms): the caller's array, which is uploaded, merged into and downloaded instead; either
 // way nothing of the caller's is written unless the whole call succeeds.
@@ -247,15 +296,8 @@ static int moments_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *gro
     Carver pairs_scratch(p);
     mdb_moments_cell *partials = pairs_scratch.take<mdb_moments_cell>(cap);
     unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_moments_cell)) + 256, &p)) return 1;
-    mdb_moments_cell *tree_values = static_cast<mdb_moments_cell *>(p);
-    unsigned long long *tree_keys = reinterpret_cast<unsigned long long *>(tree_values + tree_entries);
+    MomentsTreeScratch tree_scratch;
+    if (moments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
     const unsigned long long max_key = (unsigned long long)(n_cells - 1);
     const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
 
@@ -283,36 +325,7 @@ static int moments_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *gro
         MDB_HIP_CHECK(hipGetLastError());
         if (read_back[0]) return fail(describe_error(read_back[0]));
 
-        MomentsTree tree = {};
-        tree.keys[0] = keys;
-        tree.values[0] = partials;
-        tree.n[0] = m;
-        tree.order = nullptr;
-        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-        }
-        // The tree's levels over this slice, then the fold.
-        tree.levels = 1;
-        uint64_t used = 0;
-        {
-            LaunchTimer timer(ctx, "k_moments_tree");
-            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-                unsigned long long *level_keys = tree_keys + used;
-                mdb_moments_cell *level_values = tree_values + used;
-                hipLaunchKernelGGL(k_moments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                                   tree.levels - 1, level_keys, level_values);
-                tree.keys[tree.levels] = level_keys;
-                tree.values[tree.levels] = level_values;
-                tree.n[tree.levels] = up;
-                used += up + 1;
-                size = up;
-            }
-        }
-        {
-            LaunchTimer timer(ctx, "k_moments_fold");
-            hipLaunchKernelGGL(k_moments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-        }
+        if (moments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
     }
     // (every slice has been found free of errors: the caller's cells are written now, and only now)
     if (host_cells)

@@ -95,6 +95,18 @@ int moments_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint
 
 namespace mdb {
 
+// mdb_moments.hip, for the operators whose partials are moments cells (mdb_binned.hip too). The upper levels of the
+// reduction tree over slices of at most `cap` entries (SCRATCH_BUCKET_TREE), and one slice folded: the m entries
+// {keys[j], partials[j]} - `unsorted`: what bucket_keys_check found, the keys are then sorted by key_bits bits, stably -
+// reduced by k_moments_tree and merged into cells[key] by k_moments_fold, enqueued on the context's stream.
+struct MomentsTreeScratch {
+    mdb_moments_cell *values;
+    unsigned long long *keys;
+};
+int moments_tree_reserve(mdb_ctx *ctx, uint64_t cap, MomentsTreeScratch *out);
+int moments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_moments_cell *partials, uint64_t m, bool unsorted,
+                       unsigned int key_bits, const MomentsTreeScratch &scratch, mdb_moments_cell *cells);
+
 __device__ __forceinline__ mdb_moments_cell moments_empty() { return mdb_moments_cell{0, 0.0, 0.0}; }
 
 // The model points [a, b] of a PMC-Mean or Swing segment with regular timestamps, merged into `acc`. PMC-Mean: n equal

@@ -845,6 +845,64 @@ impl Context {
         })
     }
 
+    /// The moments of one field per value cell of another - the power curve: per bucket of
+    /// `date_bin(width, ts, origin)`, group and cell of `x` the count, the mean and `m2` of the `y` values of the pairs
+    /// whose `x` value falls in the cell (the cell rule of [`hist_cell_of`] under `edges`). The pairs are those of
+    /// [`Context::comoments_buckets`]. `cells` is row-major `[n_groups][n_buckets][edges.len() + 1]` (fresh:
+    /// `MomentsCell::default()`); the batches are merged into it and a cell without pairs stays as it was, so
+    /// [`moments_merge`] and [`moments_variance`] apply. `request.which_mask` must be 0.
+    pub fn binned_buckets(
+        &self,
+        x: &SegmentsView,
+        y: &SegmentsView,
+        group_of_segment_x: Option<&[u32]>,
+        request: &BucketRequest,
+        edges: &[f32],
+        cells: &mut [MomentsCell],
+    ) -> Result<()> {
+        check_hist_bucket_cells(request, edges.len() as u64 + 1, cells.len())?;
+        check_group_ids(x, group_of_segment_x)?;
+        let groups = group_of_segment_x.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_binned_buckets(self.raw(), &x.raw, &y.raw, groups, request, edges.as_ptr(), n_edges, cells.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::binned_buckets`] for several batches per field (rows in the order of each slice), merged as one
+    /// batch per field: the cuts of `xs` and `ys` need not coincide. `group_of_segment_x`: `None`, or one entry per
+    /// batch of `xs` (`None`: that batch's rows in group 0).
+    pub fn binned_buckets_list(
+        &self,
+        xs: &[SegmentsView],
+        ys: &[SegmentsView],
+        group_of_segment_x: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        edges: &[f32],
+        cells: &mut [MomentsCell],
+    ) -> Result<()> {
+        check_hist_bucket_cells(request, edges.len() as u64 + 1, cells.len())?;
+        if let Some(groups) = group_of_segment_x {
+            if groups.len() != xs.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), xs.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(xs.len());
+        for (k, view) in xs.iter().enumerate() {
+            let groups = group_of_segment_x.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let x_inputs: Vec<*const sys::mdb_segments> = xs.iter().map(|view| &view.raw as *const _).collect();
+        let y_inputs: Vec<*const sys::mdb_segments> = ys.iter().map(|view| &view.raw as *const _).collect();
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_binned_buckets_list(self.raw(), x_inputs.as_ptr(), x_inputs.len() as u32, y_inputs.as_ptr(),
+                                         y_inputs.len() as u32, group_pointers.as_ptr(), request, edges.as_ptr(), n_edges,
+                                         cells.as_mut_ptr())
+        })
+    }
+
     /// A histogram of the values of `segments` inside `time_range`, without materialising a data point: replaces
     /// GridExec -> AggregateExec for a distribution. `counts` is row-major `[n_groups][edges.len() + 1]` and the
     /// points are ADDED to it; a value falls in the cell numbered by the edges at or below it in totalOrder.

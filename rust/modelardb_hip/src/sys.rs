@@ -448,6 +448,17 @@ unsafe extern "C" {
     pub fn mdb_comoments_merge_n(into: *mut mdb_comoments_cell, from: *const mdb_comoments_cell, n: u64) -> c_int;
     pub fn mdb_comoments_moments(cells: *const mdb_comoments_cell, n: u64, which: u32, out: *mut mdb_moments_cell) -> c_int;
     pub fn mdb_comoments_finish(cells: *const mdb_comoments_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
+    // ---- moments of one field per value cell of another (include/mdb.h) ----
+    pub fn mdb_binned_buckets(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                              group_of_segment_x: *const u32, request: *const mdb_bucket_request, edges: *const f32,
+                              n_edges: u32, inout: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_binned_buckets_dev(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                                  group_of_segment_x: *const u32, request: *const mdb_bucket_request, edges: *const f32,
+                                  n_edges: u32, inout: *mut mdb_moments_cell) -> c_int;
+    pub fn mdb_binned_buckets_list(ctx: *mut mdb_ctx, xs: *const *const mdb_segments, n_x: u32,
+                                   ys: *const *const mdb_segments, n_y: u32,
+                                   group_of_segment_x: *const *const u32, request: *const mdb_bucket_request,
+                                   edges: *const f32, n_edges: u32, inout: *mut mdb_moments_cell) -> c_int;
     pub fn mdb_quantile_batch(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
                               n_q: u32, out_lo: *mut f32, out_hi: *mut f32, n_points: *mut u64) -> c_int;
     pub fn mdb_quantile_batch_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, t_lo: i64, t_hi: i64, q: *const f64,
