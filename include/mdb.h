@@ -701,6 +701,53 @@ int mdb_binned_buckets_list(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_
                             const mdb_bucket_request *request, const float *edges, uint32_t n_edges,
                             mdb_moments_cell *inout);
 
+/* Extension: the linear trend of a field over TIME - per bucket of date_bin(width, ts, origin) and group one
+ * mdb_comoments_cell with x = the time offset of the point inside its bucket and y = its value:
+ *   SELECT turbine, date_bin(...), regr_slope(bearing_temp, ts), regr_r2(bearing_temp, ts), corr(bearing_temp, ts)
+ *   ... GROUP BY 1, 2
+ * mdb_comoments_buckets* cannot answer this: its y is a second field column of segments, and a timestamp is not one
+ * (it does not fit an f32). The reference answers with GridExec -> AggregateExec over every rebuilt point. Here the
+ * time side needs no data: on regular timestamps the sums of x over a run of n points are closed forms in n and the
+ * sampling interval, a PMC-Mean segment gives its whole cell per bucket in O(1), a Swing segment needs only its values
+ * point by point in registers. No y column, no scratch beyond the pairs.
+ *   request: mdb_bucket_request, unchanged; which_mask must be 0. inout: row-major [n_groups][n_buckets] cells
+ *     (mdb_comoments_cell, mdb_format.h); a fresh cell is all-zero bytes. A call MERGES into it.
+ *   Which points: exactly those mdb_moments_buckets* counts for the same batch, groups and request; the checks, the
+ *     errors and "inout untouched on error" are the same.
+ *   x: for a counted point with timestamp t in bucket b, x = (double)(uint64_t)((t - origin) - b * width): it lies in
+ *     [0, width), is formed in wrapping-exact integer arithmetic and converted once; exact below 2^53. x is relative
+ *     to the bucket so that f64 keeps every digit at any epoch. regr_slope, corr, regr_r2 and covar_* do not depend on
+ *     a shift of x: they are SQL's values for (field, ts). MDB_COMOMENTS_REGR_INTERCEPT is the fitted value at the
+ *     bucket's first instant (what a chart needs); SQL's regr_intercept(field, ts) is that minus
+ *     slope * (origin + b * width) - at epoch scale that subtraction cancels, whoever performs it.
+ *   y: (double)v. count, mean_y and m2_y are the moments of the field.
+ *   Run rule: a run (the points of one segment in one bucket, or of one piece of a stream in one bucket) is summed
+ *     around its first pair as for mdb_comoments_buckets, with dx = the integer difference t - t_first converted to
+ *     double (k * delta on regular timestamps). Runs meet only in the merge rule of mdb_comoments_merge_n.
+ *     On regular timestamps n points at x0 + k * delta have mean_x = x0 + delta * (n-1)/2 and
+ *     m2_x = delta^2 * n(n^2-1)/12; a PMC-Mean run adds mean_y = v and m2_y = c_xy = v - v.
+ *   Merge and finish: mdb_comoments_merge_n, mdb_comoments_moments and mdb_comoments_finish, unchanged; x is the
+ *     independent variable already.
+ *   Exact promises: count equals mdb_agg_buckets' COUNT, always. A cell whose values are all equal and finite has
+ *     m2_y == 0.0, c_xy == 0.0 and, with two or more distinct timestamps, slope == 0.0 exactly. A cell of one point, or
+ *     of points that all share one timestamp, has m2_x == 0.0: the regr_* and corr kinds give NaN. A NaN or an infinity
+ *     among the values makes mean_y, m2_y and c_xy non-finite; mean_x and m2_x stay finite and correct.
+ *   Determinism, as for mdb_moments_buckets: two runs and the three forms agree bit for bit; the order of segments,
+ *     the cut of batches and MDB_AGG_BUCKET_SLICE_PAIRS move the five doubles by rounding only.
+ *   Origin invariance: moving the origin by a whole number of widths, with n_buckets moved along, gives the same bytes
+ *     in the cells that still exist.
+ *   Time unit: microseconds, as mdb_bucket_request states; the slope is per microsecond.
+ *   Errors (mdb_last_error set, inout untouched): those of mdb_moments_buckets*. An empty batch or n_buckets == 0
+ *     succeeds and changes nothing. */
+int mdb_trend_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                      const mdb_bucket_request *request, mdb_comoments_cell *inout);
+/* All device pointers: the batch, group_of_segment and inout are in HBM. */
+int mdb_trend_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                          const mdb_bucket_request *request, mdb_comoments_cell *inout);
+/* Several host batches (rows in the order of the list) folded as one batch; group_of_segment: one array per batch, or NULL. */
+int mdb_trend_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                           uint32_t n_inputs, const mdb_bucket_request *request, mdb_comoments_cell *inout);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -326,6 +326,12 @@ _HIP_SYMBOLS = {
     "mdb_comoments_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_comoments_moments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_comoments_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_trend_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                    C.c_void_p]),
+    "mdb_trend_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
+                                        C.c_void_p]),
+    "mdb_trend_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                         C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
     "mdb_binned_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
                                      C.POINTER(BucketRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
     "mdb_binned_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,

@@ -1192,6 +1192,77 @@ class Context:
             raise ValueError("the data inside the range spans more than one bucket can hold: use comoments_buckets")
         return self.comoments_buckets(x, y, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
 
+    # ---- linear trend of a field over time: comoments cells with x = the time offset inside the bucket ----------
+
+    def trend_buckets(self, batch, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                      n_groups=None):
+        """The trend of one field over time per bucket of date_bin(width, ts, origin) and group (mdb_trend_buckets):
+        cells of COMOMENTS_CELL_DTYPE with x = the time offset of a point inside its bucket (microseconds, in
+        [0, width)) and y = its value. Returns `cells` (or fresh ones), shape (n_groups, n_buckets), merged in place.
+        `groups` and n_groups as for agg_buckets; comoments_finish gives regr_slope (per microsecond), regr_r2, corr
+        and covar_*, and "regr_intercept" the fitted value at the bucket's first instant."""
+        return self.trend_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups],
+                                       t_lo, t_hi, cells, n_groups)
+
+    def trend_buckets_list(self, batches, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                           n_groups=None):
+        """Several host batches merged as one (mdb_trend_buckets_list); `groups`: None or one array (or None) per
+        batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._comoments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_trend_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                    C.byref(request), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def trend_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                          cells=None, n_groups=None):
+        """mdb_trend_buckets_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._comoments_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_trend_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                       None if dev_groups is None else C.c_void_p(dev_groups),
+                                                       C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, COMOMENTS_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def trend(self, batch, t_lo=None, t_hi=None, groups=None, n_groups=None, origin=None):
+        """(cells, origin): the trend cells of the points of `batch` inside [t_lo, t_hi], one per group (shape
+        (n_groups,)) - one bucket over the data inside the range - and the instant x is counted from. By default that
+        is the first instant of the bucket (the first timestamp the range can hold); it is returned so the caller can
+        place the line: value(t) = regr_intercept + regr_slope * (t - origin). A given `origin` must not lie behind
+        that instant."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        if len(batch) == 0:
+            return fresh_comoments_cells(n_groups), 0 if origin is None else int(origin)
+        lo, hi = int(np.min(batch.start_time)), int(np.max(batch.end_time))
+        lo = lo if t_lo is None else max(lo, int(t_lo))
+        hi = hi if t_hi is None else min(hi, int(t_hi))
+        origin = lo if origin is None else int(origin)
+        if lo > hi:
+            return fresh_comoments_cells(n_groups), origin
+        if origin > lo:
+            raise ValueError("origin must not lie behind the first instant of the data inside the range")
+        if hi - origin + 1 > INT64_MAX:
+            raise ValueError("the data inside the range spans more than one bucket can hold: use trend_buckets")
+        cells = self.trend_buckets(batch, origin, hi - origin + 1, 1, groups, lo, hi, None, n_groups)
+        return cells.reshape(n_groups), origin
+
     # ---- moments of one field per value cell of another: count, mean and m2 of y per cell of x ----------
 
     @staticmethod

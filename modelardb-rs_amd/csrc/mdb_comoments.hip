@@ -221,6 +221,56 @@ __global__ __launch_bounds__(MDB_WAVE) void k_comoments_pieces(
     if (error) atomicOr(error_out, error);
 }
 
+int comoments_tree_reserve(mdb_ctx *ctx, uint64_t cap, ComomentsTreeScratch *out) {
+    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
+    uint64_t tree_entries = 0;
+    for (uint64_t m = cap; m > BUCKET_TILE;) {
+        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
+        tree_entries += m + 1;
+    }
+    void *p;
+    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_comoments_cell)) + 256, &p)) return 1;
+    out->values = static_cast<mdb_comoments_cell *>(p);
+    out->keys = reinterpret_cast<unsigned long long *>(out->values + tree_entries);
+    return 0;
+}
+
+int comoments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_comoments_cell *partials, uint64_t m,
+                         bool unsorted, unsigned int key_bits, const ComomentsTreeScratch &scratch,
+                         mdb_comoments_cell *cells) {
+    ComomentsTree tree = {};
+    tree.keys[0] = keys;
+    tree.values[0] = partials;
+    tree.n[0] = m;
+    tree.order = nullptr;
+    if (unsorted) { // keys out of order: a stable sort by key, pair numbers alongside
+        if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
+    }
+    // The tree's levels over this slice, then the fold.
+    tree.levels = 1;
+    uint64_t used = 0;
+    {
+        LaunchTimer timer(ctx, "k_comoments_tree");
+        for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
+            const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
+            unsigned long long *level_keys = scratch.keys + used;
+            mdb_comoments_cell *level_values = scratch.values + used;
+            hipLaunchKernelGGL(k_comoments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
+                               tree.levels - 1, level_keys, level_values);
+            tree.keys[tree.levels] = level_keys;
+            tree.values[tree.levels] = level_values;
+            tree.n[tree.levels] = up;
+            used += up + 1;
+            size = up;
+        }
+    }
+    {
+        LaunchTimer timer(ctx, "k_comoments_fold");
+        hipLaunchKernelGGL(k_comoments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
+    }
+    return 0;
+}
+
 // The rows of x and y under [t_lo, t_hi] compared, x's first rows (n + 1, in SCRATCH_COMOMENTS_ROWS: a slot of its
 // own, the range grid of y and the row masks use theirs meanwhile) and the y column (SCRATCH_COMOMENTS_YCOL).
 int comoments_rows(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, int64_t t_lo, int64_t t_hi,
@@ -304,15 +354,8 @@ static int comoments_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segment
     Carver pairs_scratch(p);
     mdb_comoments_cell *partials = pairs_scratch.take<mdb_comoments_cell>(cap);
     unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_comoments_cell)) + 256, &p)) return 1;
-    mdb_comoments_cell *tree_values = static_cast<mdb_comoments_cell *>(p);
-    unsigned long long *tree_keys = reinterpret_cast<unsigned long long *>(tree_values + tree_entries);
+    ComomentsTreeScratch tree_scratch;
+    if (comoments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
     const unsigned long long max_key = (unsigned long long)(n_cells - 1);
     const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
 
@@ -344,36 +387,7 @@ static int comoments_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segment
                         "disagree.");
         if (read_back[0]) return fail(describe_error(read_back[0]));
 
-        ComomentsTree tree = {};
-        tree.keys[0] = keys;
-        tree.values[0] = partials;
-        tree.n[0] = m;
-        tree.order = nullptr;
-        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-        }
-        // The tree's levels over this slice, then the fold.
-        tree.levels = 1;
-        uint64_t used = 0;
-        {
-            LaunchTimer timer(ctx, "k_comoments_tree");
-            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-                unsigned long long *level_keys = tree_keys + used;
-                mdb_comoments_cell *level_values = tree_values + used;
-                hipLaunchKernelGGL(k_comoments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                                   tree.levels - 1, level_keys, level_values);
-                tree.keys[tree.levels] = level_keys;
-                tree.values[tree.levels] = level_values;
-                tree.n[tree.levels] = up;
-                used += up + 1;
-                size = up;
-            }
-        }
-        {
-            LaunchTimer timer(ctx, "k_comoments_fold");
-            hipLaunchKernelGGL(k_comoments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-        }
+        if (comoments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
     }
     // (every slice has been found free of errors: the caller's cells are written now, and only now)
     if (host_cells)

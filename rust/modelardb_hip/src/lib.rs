@@ -845,6 +845,54 @@ impl Context {
         })
     }
 
+    /// The linear trend of a field over time: per bucket of `date_bin(width, ts, origin)` and group one
+    /// [`ComomentsCell`] with `x` = the time offset of a point inside its bucket (microseconds, in `[0, width)`) and
+    /// `y` = its value - `regr_slope(field, ts)`, `regr_r2`, `corr` and `covar_*` follow with [`comoments_finish`],
+    /// whose intercept is the fitted value at the bucket's first instant. The points are those of
+    /// [`Context::moments_buckets`]; no point is materialised and no timestamp column is built. `cells` is row-major
+    /// `[n_groups][n_buckets]` (fresh: `ComomentsCell::default()`); the batch is merged into it, and a cell without
+    /// points stays as it was, so [`comoments_merge`] applies. `request.which_mask` must be 0.
+    pub fn trend_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &BucketRequest,
+        cells: &mut [ComomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_trend_buckets(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::trend_buckets`] for several batches at once (rows in the order of the slice), merged as one batch.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn trend_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        cells: &mut [ComomentsCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_trend_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                        request, cells.as_mut_ptr())
+        })
+    }
+
     /// The moments of one field per value cell of another - the power curve: per bucket of
     /// `date_bin(width, ts, origin)`, group and cell of `x` the count, the mean and `m2` of the `y` values of the pairs
     /// whose `x` value falls in the cell (the cell rule of [`hist_cell_of`] under `edges`). The pairs are those of

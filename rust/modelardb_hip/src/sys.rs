@@ -448,6 +448,14 @@ unsafe extern "C" {
     pub fn mdb_comoments_merge_n(into: *mut mdb_comoments_cell, from: *const mdb_comoments_cell, n: u64) -> c_int;
     pub fn mdb_comoments_moments(cells: *const mdb_comoments_cell, n: u64, which: u32, out: *mut mdb_moments_cell) -> c_int;
     pub fn mdb_comoments_finish(cells: *const mdb_comoments_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
+    // ---- linear trend of a field over time: comoments cells with x = the time offset in the bucket (include/mdb.h) ----
+    pub fn mdb_trend_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                             request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
+    pub fn mdb_trend_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                 request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
+    pub fn mdb_trend_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                  group_of_segment: *const *const u32, n_inputs: u32,
+                                  request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
     // ---- moments of one field per value cell of another (include/mdb.h) ----
     pub fn mdb_binned_buckets(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
                               group_of_segment_x: *const u32, request: *const mdb_bucket_request, edges: *const f32,
