@@ -748,6 +748,86 @@ int mdb_trend_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *
 int mdb_trend_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                            uint32_t n_inputs, const mdb_bucket_request *request, mdb_comoments_cell *inout);
 
+/* Extension: EPISODES - the maximal runs of points that pass a value predicate: when was bearing_temp > 85, for how
+ * long each time, and how bad was it. In SQL the gaps-and-islands pattern (lag() over the filtered rows, GROUP BY
+ * island), for which the reference rebuilds every point (GridExec -> FilterExec -> WindowAggExec -> AggregateExec).
+ * Here a segment is summarised in O(1) (PMC-Mean) or two binary searches (Swing), the summaries are stitched by a
+ * device-wide scan, and only the episodes leave the device.
+ *   Rows: those of mdb_grid_batch_range(in, filter.t_lo, filter.t_hi), in that order - the row numbering of the
+ *     masks. Row r has timestamp ts(r), value v(r), segment row seg(r) and group g(r) = group_of_segment[seg(r)]
+ *     (group_of_segment NULL: 0).
+ *   Passing: row r passes iff v(r) passes the filter's value bounds in totalOrder: the set bits of mdb_mask_filter_dev.
+ *   Continuing: row r >= 1 continues row r-1 iff g(r) == g(r-1) and ts(r) >= ts(r-1) and ts(r) - ts(r-1) <= max_gap
+ *     (the difference formed as uint64_t after the comparison). The rule holds for every pair of consecutive rows,
+ *     inside a segment or across segments: a step backwards in time ends an episode, as when the next series
+ *     begins. max_gap == INT64_MAX switches the gap rule off.
+ *   Episode: a maximal set of consecutive rows that all pass, each but the first continuing its predecessor;
+ *     reported iff count >= min_count and t_last - t_first >= min_duration. Episodes come out ordered by first_row.
+ *   Exact promises: every field but `sum` is exact; sum is the f64 sum of the f32 values within 0.001 % of the sum
+ *     of their magnitudes. With both minimum filters off the episodes are disjoint and the union of
+ *     [first_row, first_row + count) is exactly the set bits of mdb_mask_filter_dev. An episode of equal finite
+ *     values has min == max == that value.
+ *   Determinism: for the same input, request and form two runs agree byte for byte, and the four forms agree byte
+ *     for byte; no float atomics, and no grouping of f64 additions depends on timing. MDB_FILTER_SLICE_POINTS may
+ *     move `sum` by rounding only.
+ *   Errors (mdb_last_error set, outputs untouched): a NULL argument, unknown filter flag bits or reserved != 0,
+ *     flags != 0, a negative max_gap or min_duration, n_groups == 0, a group id >= n_groups on ANY segment of the
+ *     batch (inside the time range or not), a too small cap, the error classes of the range calls. What can be
+ *     checked without the device is checked before the device is used. An empty batch, an empty time range and an
+ *     empty value interval are valid and give no episode. */
+typedef struct mdb_episode {      /* 64 bytes */
+    uint64_t first_row;           /* row number as defined above */
+    uint64_t count;               /* rows first_row .. first_row + count - 1 */
+    int64_t  t_first, t_last;
+    double   sum;                 /* f64 sum of the f32 values */
+    float    min, max;            /* as mdb_agg_state folds them: fmin / fmax from FLT_MAX / -FLT_MAX, a NaN is skipped */
+    uint32_t group;
+    uint32_t first_segment;       /* segment row of the batch (of the list) that holds first_row */
+    uint64_t reserved;            /* 0 */
+} mdb_episode;
+
+typedef struct mdb_episodes_request {   /* 64 bytes */
+    mdb_value_filter filter;
+    int64_t  max_gap;             /* >= 0 */
+    int64_t  min_duration;        /* >= 0 */
+    uint64_t min_count;           /* 0 and 1: every episode */
+    uint32_t n_groups;            /* >= 1 */
+    uint32_t flags;               /* must be 0 */
+} mdb_episodes_request;
+
+typedef struct mdb_episodes_result {
+    mdb_episode *episodes;        /* host memory, n of them (NULL if n == 0) */
+    uint64_t n, n_rows, n_passing;
+    void *priv_;
+} mdb_episodes_result;
+
+MDB_LAYOUT_ASSERT(sizeof(mdb_episode) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episode, sum) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episode, min) == 40);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episode, group) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episode, reserved) == 56);
+MDB_LAYOUT_ASSERT(sizeof(mdb_episodes_request) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episodes_request, max_gap) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_episodes_request, n_groups) == 56);
+
+/* The batch and group_of_segment (may be NULL) in HBM. n_rows: the rows under the time range; n_passing: the passing
+ * ones (the sum of the count fields only when both minimum filters are off). */
+int mdb_episodes_count_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                           const mdb_episodes_request *request, uint64_t *n_episodes, uint64_t *n_rows,
+                           uint64_t *n_passing);
+/* ... and the episodes into out (HBM, room for cap of them). A too small cap fails and writes nothing. */
+int mdb_episodes_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                     const mdb_episodes_request *request, mdb_episode *out, uint64_t cap, uint64_t *n_out,
+                     uint64_t *n_rows, uint64_t *n_passing);
+/* Host batch and host group_of_segment (may be NULL); only the episodes cross PCIe on the way back. */
+int mdb_episodes(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                 const mdb_episodes_request *request, mdb_episodes_result **out);
+/* Several host batches (rows in the order of the list) folded as one batch: an episode may cross from one input to
+ * the next, first_segment counts through the list. group_of_segment: one array per batch, or NULL. */
+int mdb_episodes_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                      uint32_t n_inputs, const mdb_episodes_request *request, mdb_episodes_result **out);
+void mdb_episodes_result_free(mdb_episodes_result *result);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

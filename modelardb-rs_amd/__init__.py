@@ -14,6 +14,6 @@ from ._abi import (  # noqa: F401
 )
 from .segments import BinaryViewColumn, SegmentBatch, error_bound  # noqa: F401
 from .api import (  # noqa: F401
-    AGG_STATE_DTYPE, COMOMENTS_CELL_DTYPE, COMOMENTS_KINDS, M4_CELL_DTYPE, MOMENTS_CELL_DTYPE, Context, DeviceSegments, HipError, agg_merge_n, are_compressed_timestamps_regular,
+    AGG_STATE_DTYPE, COMOMENTS_CELL_DTYPE, EPISODE_DTYPE, COMOMENTS_KINDS, M4_CELL_DTYPE, MOMENTS_CELL_DTYPE, Context, DeviceSegments, HipError, agg_merge_n, are_compressed_timestamps_regular,
     comm_unique_id, comoments_finish, comoments_merge, comoments_moments, fresh_agg_states, fresh_comoments_cells, fresh_m4_cells, fresh_moments_cells, hist_cell_of, m4_merge, mask_words, moments_merge, moments_variance, quantile_positions, unpack_mask, is_value_within_error_bound, value_filter, value_filter_bits,
 )

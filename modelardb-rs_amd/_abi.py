@@ -182,6 +182,47 @@ class ValueFilterC(C.Structure):
     ]
 
 
+class EpisodeC(C.Structure):
+    """mdb_episode: one maximal run of passing rows (mdb_episodes*)."""
+    _fields_ = [
+        ("first_row", C.c_uint64),
+        ("count", C.c_uint64),
+        ("t_first", C.c_int64),
+        ("t_last", C.c_int64),
+        ("sum", C.c_double),
+        ("min", C.c_float),
+        ("max", C.c_float),
+        ("group", C.c_uint32),
+        ("first_segment", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class EpisodesRequestC(C.Structure):
+    """mdb_episodes_request: the value filter, the gap rule and the minimum filters of mdb_episodes*."""
+    _fields_ = [
+        ("filter", ValueFilterC),
+        ("max_gap", C.c_int64),
+        ("min_duration", C.c_int64),
+        ("min_count", C.c_uint64),
+        ("n_groups", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class EpisodesResultC(C.Structure):
+    _fields_ = [
+        ("episodes", C.c_void_p),
+        ("n", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("n_passing", C.c_uint64),
+        ("priv_", C.c_void_p),
+    ]
+
+
+assert C.sizeof(EpisodeC) == 64 and C.sizeof(EpisodesRequestC) == 64
+
+
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
     _fields_ = [
@@ -332,6 +373,15 @@ _HIP_SYMBOLS = {
                                         C.c_void_p]),
     "mdb_trend_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
                                          C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,
+                                   C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mdb_episodes": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
+                               C.POINTER(C.POINTER(EpisodesResultC))]),
+    "mdb_episodes_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                    C.POINTER(EpisodesRequestC), C.POINTER(C.POINTER(EpisodesResultC))]),
+    "mdb_episodes_result_free": (None, [C.POINTER(EpisodesResultC)]),
     "mdb_binned_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
                                      C.POINTER(BucketRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
     "mdb_binned_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,

@@ -263,6 +263,11 @@ def comoments_finish(cells, kind):
     return out.reshape(cells.shape)
 
 
+EPISODE_DTYPE = np.dtype([("first_row", "<u8"), ("count", "<u8"), ("t_first", "<i8"), ("t_last", "<i8"), ("sum", "<f8"),
+                          ("min", "<f4"), ("max", "<f4"), ("group", "<u4"), ("first_segment", "<u4"), ("reserved", "<u8")])
+assert EPISODE_DTYPE.itemsize == C.sizeof(_abi.EpisodeC) == 64
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -1262,6 +1267,96 @@ class Context:
             raise ValueError("the data inside the range spans more than one bucket can hold: use trend_buckets")
         cells = self.trend_buckets(batch, origin, hi - origin + 1, 1, groups, lo, hi, None, n_groups)
         return cells.reshape(n_groups), origin
+
+    # ---- episodes: the maximal runs of points that pass a value predicate ----------------------------------------
+
+    @staticmethod
+    def _episodes_request(flt, n_groups, max_gap, min_duration, min_count):
+        request = _abi.EpisodesRequestC()
+        C.memmove(C.addressof(request), C.addressof(flt), C.sizeof(_abi.ValueFilterC))
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.min_duration = int(min_duration)
+        request.min_count = int(min_count)
+        request.n_groups = int(n_groups)
+        request.flags = 0
+        return request
+
+    def episodes(self, batch, flt, groups=None, n_groups=None, max_gap=None, min_duration=0, min_count=0):
+        """(episodes, n_rows, n_passing): the maximal runs of rows of `batch` that pass `flt` (value_filter(...): value
+        bounds and time range), each row continuing its predecessor - same group, time not stepping back, at most
+        max_gap later (None: no gap rule) - as a structured array of EPISODE_DTYPE ordered by first_row
+        (mdb_episodes). Rows are numbered as the masks number them. Only episodes of at least min_count rows and
+        min_duration microseconds are reported; n_passing counts every passing row. `groups`: one id per segment row
+        (None: all in group 0)."""
+        return self.episodes_list([batch], flt, None if groups is None else [groups], n_groups, max_gap, min_duration,
+                                  min_count)
+
+    def episodes_list(self, batches, flt, groups=None, n_groups=None, max_gap=None, min_duration=0, min_count=0):
+        """Several host batches folded as one (mdb_episodes_list): an episode may cross from one batch to the next,
+        first_segment counts through the list. `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        request = self._episodes_request(flt, self._n_groups(n_groups, None, batch_groups), max_gap, min_duration,
+                                         min_count)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        out = C.POINTER(_abi.EpisodesResultC)()
+        self._check(self.lib.mdb_episodes_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                               C.byref(out)))
+        try:
+            result = out.contents
+            n = int(result.n)
+            if n == 0:
+                episodes = np.zeros(0, dtype=EPISODE_DTYPE)
+            else:
+                buffer = (C.c_char * (n * EPISODE_DTYPE.itemsize)).from_address(result.episodes)
+                episodes = np.frombuffer(buffer, dtype=EPISODE_DTYPE).copy()
+            return episodes, int(result.n_rows), int(result.n_passing)
+        finally:
+            self.lib.mdb_episodes_result_free(out)
+
+    def episodes_count_dev(self, dev_segments, flt, groups_ptr=None, n_groups=1, max_gap=None, min_duration=0,
+                           min_count=0):
+        """mdb_episodes_count_dev on a resident batch (groups_ptr: a device array or None): (n_episodes, n_rows,
+        n_passing)."""
+        request = self._episodes_request(flt, n_groups, max_gap, min_duration, min_count)
+        n, n_rows, n_passing = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mdb_episodes_count_dev(self.handle, C.byref(dev_segments.seg), C.c_void_p(groups_ptr),
+                                                    C.byref(request), C.byref(n), C.byref(n_rows), C.byref(n_passing)))
+        return n.value, n_rows.value, n_passing.value
+
+    def episodes_into_dev(self, dev_segments, flt, out_ptr, cap, groups_ptr=None, n_groups=1, max_gap=None,
+                          min_duration=0, min_count=0):
+        """mdb_episodes_dev into `cap` device episodes at out_ptr: (n_out, n_rows, n_passing)."""
+        request = self._episodes_request(flt, n_groups, max_gap, min_duration, min_count)
+        n, n_rows, n_passing = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.mdb_episodes_dev(self.handle, C.byref(dev_segments.seg), C.c_void_p(groups_ptr),
+                                              C.byref(request), C.c_void_p(out_ptr), int(cap), C.byref(n),
+                                              C.byref(n_rows), C.byref(n_passing)))
+        return n.value, n_rows.value, n_passing.value
+
+    def episodes_dev(self, dev_segments, flt, groups=None, n_groups=None, max_gap=None, min_duration=0, min_count=0):
+        """episodes() on a resident batch: `groups` is uploaded, the episodes are counted, written on the device
+        (mdb_episodes_count_dev, mdb_episodes_dev) and downloaded."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, None, [groups])
+        dev_groups = None if groups is None else self.upload_array(groups)
+        out = None
+        try:
+            n, _, _ = self.episodes_count_dev(dev_segments, flt, dev_groups, n_groups, max_gap, min_duration, min_count)
+            out = self.dev_alloc(EPISODE_DTYPE.itemsize * max(n, 1))
+            produced, n_rows, n_passing = self.episodes_into_dev(dev_segments, flt, out, n, dev_groups, n_groups, max_gap,
+                                                                 min_duration, min_count)
+            assert produced == n
+            episodes = self.download_array(out, n, EPISODE_DTYPE) if n else np.zeros(0, dtype=EPISODE_DTYPE)
+            return episodes, n_rows, n_passing
+        finally:
+            if out is not None:
+                self.dev_free(out)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
 
     # ---- moments of one field per value cell of another: count, mean and m2 of y per cell of x ----------
 

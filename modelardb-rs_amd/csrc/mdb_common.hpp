@@ -100,6 +100,8 @@ enum ScratchSlot {
     SCRATCH_COMOMENTS_ROWS,      // mdb_comoments_buckets*: rows and first rows of the x field's segments, the scan's sums
     SCRATCH_COMOMENTS_YCOL,      // ... the y column: one f32 per row of the y field under the time range
     SCRATCH_BINNED,              // mdb_binned_buckets*: run counts and offsets per x segment, the scan's sums, the edges' keys
+    SCRATCH_EPISODES_SEGMENTS,   // mdb_episodes*: per segment its rows, first row, summary, prefix, counts and the scans
+    SCRATCH_EPISODES_OUT,        // ... the episodes of the host forms before they are copied back
     SCRATCH_SLOT_COUNT
 };
 

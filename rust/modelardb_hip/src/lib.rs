@@ -34,7 +34,7 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
     mdb_comoments_cell as ComomentsCell, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
-    mdb_moments_cell as MomentsCell,
+    mdb_episode as Episode, mdb_episodes_request as EpisodesRequest, mdb_moments_cell as MomentsCell,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
@@ -441,6 +441,19 @@ pub fn quantile_positions(q: f64, n_points: u64) -> Result<(u64, u64, f64)> {
 }
 
 /// Group ids of a bucket call: one per segment row, if given.
+/// Copies the episodes of a result out and frees it.
+fn take_episodes(out: *mut sys::mdb_episodes_result) -> (Vec<Episode>, u64, u64) {
+    let result = unsafe { &*out };
+    let episodes = if result.n == 0 {
+        Vec::new()
+    } else {
+        unsafe { std::slice::from_raw_parts(result.episodes, result.n as usize) }.to_vec()
+    };
+    let counts = (result.n_rows, result.n_passing);
+    unsafe { sys::mdb_episodes_result_free(out) };
+    (episodes, counts.0, counts.1)
+}
+
 fn check_group_ids(segments: &SegmentsView, group_of_segment: Option<&[u32]>) -> Result<()> {
     if let Some(groups) = group_of_segment {
         if groups.len() as u64 != segments.raw.n {
@@ -891,6 +904,53 @@ impl Context {
             sys::mdb_trend_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                         request, cells.as_mut_ptr())
         })
+    }
+
+    /// Episodes: the maximal runs of rows that pass the request's value filter, each row but the first continuing
+    /// its predecessor - same group, time not stepping back, at most `request.max_gap` later - ordered by
+    /// `first_row`; SQL's gaps-and-islands over the filtered rows, computed on the segments. Rows are numbered as the
+    /// masks number them. Returns the episodes of at least `min_count` rows and `min_duration` microseconds, the rows
+    /// under the time range and the passing rows among them. Only the episodes cross PCIe.
+    pub fn episodes(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &EpisodesRequest,
+    ) -> Result<(Vec<Episode>, u64, u64)> {
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let mut out: *mut sys::mdb_episodes_result = std::ptr::null_mut();
+        check(unsafe { sys::mdb_episodes(self.raw(), &segments.raw, groups, request, &mut out) })?;
+        Ok(take_episodes(out))
+    }
+
+    /// [`Context::episodes`] for several batches at once (rows in the order of the slice), folded as one batch: an
+    /// episode may cross from one batch to the next, `first_segment` counts through the list.
+    /// `group_of_segment`: `None`, or one entry per batch (`None`: that batch's rows in group 0).
+    pub fn episodes_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &EpisodesRequest,
+    ) -> Result<(Vec<Episode>, u64, u64)> {
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        let mut out: *mut sys::mdb_episodes_result = std::ptr::null_mut();
+        check(unsafe {
+            sys::mdb_episodes_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32, request,
+                                   &mut out)
+        })?;
+        Ok(take_episodes(out))
     }
 
     /// The moments of one field per value cell of another - the power curve: per bucket of

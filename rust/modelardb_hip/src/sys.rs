@@ -268,6 +268,57 @@ pub struct mdb_comoments_cell {
     pub c_xy: f64,
 }
 
+/// One episode of `mdb_episodes*`: a maximal run of consecutive passing rows, each but the first continuing its
+/// predecessor (same group, time not stepping back, at most `max_gap` later). 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_episode {
+    /// Row number in the range grid of the batch under the filter's time range (the row numbering of the masks).
+    pub first_row: u64,
+    pub count: u64,
+    pub t_first: i64,
+    pub t_last: i64,
+    /// f64 sum of the f32 values.
+    pub sum: f64,
+    /// fmin / fmax from `f32::MAX` / `-f32::MAX`; a NaN is skipped.
+    pub min: f32,
+    pub max: f32,
+    pub group: u32,
+    /// Segment row of the batch (of the list) that holds `first_row`.
+    pub first_segment: u32,
+    pub reserved: u64,
+}
+
+/// The request of `mdb_episodes*`. 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_episodes_request {
+    pub filter: mdb_value_filter,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// >= 0.
+    pub min_duration: i64,
+    /// 0 and 1: every episode.
+    pub min_count: u64,
+    /// >= 1.
+    pub n_groups: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+#[repr(C)]
+pub struct mdb_episodes_result {
+    /// Host memory, `n` episodes (null if `n == 0`).
+    pub episodes: *mut mdb_episode,
+    pub n: u64,
+    pub n_rows: u64,
+    pub n_passing: u64,
+    pub priv_: *mut c_void,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_episode>() == 64);
+const _: () = assert!(std::mem::size_of::<mdb_episodes_request>() == 64);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -456,6 +507,19 @@ unsafe extern "C" {
     pub fn mdb_trend_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
                                   group_of_segment: *const *const u32, n_inputs: u32,
                                   request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
+    // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
+    pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                  request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
+                                  n_passing: *mut u64) -> c_int;
+    pub fn mdb_episodes_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                            request: *const mdb_episodes_request, out: *mut mdb_episode, cap: u64, n_out: *mut u64,
+                            n_rows: *mut u64, n_passing: *mut u64) -> c_int;
+    pub fn mdb_episodes(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                        request: *const mdb_episodes_request, out: *mut *mut mdb_episodes_result) -> c_int;
+    pub fn mdb_episodes_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                             group_of_segment: *const *const u32, n_inputs: u32,
+                             request: *const mdb_episodes_request, out: *mut *mut mdb_episodes_result) -> c_int;
+    pub fn mdb_episodes_result_free(result: *mut mdb_episodes_result);
     // ---- moments of one field per value cell of another (include/mdb.h) ----
     pub fn mdb_binned_buckets(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
                               group_of_segment_x: *const u32, request: *const mdb_bucket_request, edges: *const f32,
