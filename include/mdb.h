@@ -828,6 +828,58 @@ int mdb_episodes_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uin
                       uint32_t n_inputs, const mdb_episodes_request *request, mdb_episodes_result **out);
 void mdb_episodes_result_free(mdb_episodes_result *result);
 
+/* Extension: TIME-WEIGHTED averages and integrals per bucket of date_bin(width, ts, origin) and group - the series
+ * taken as a function of time, not as a set of points: energy = integral of power, the share of a window a setpoint
+ * was held, degree-hours. Elsewhere time_weight('Linear' | 'LOCF', ts, v) / integral(), or lag() over every rebuilt
+ * point followed by a weighted sum (GridExec -> WindowAggExec -> AggregateExec). Here a PMC-Mean segment's share of a
+ * bucket is value x clipped duration, a Swing segment's a closed form of its line, both O(1) per (segment, bucket).
+ *   request: mdb_integral_request (mdb_format.h). buckets.t_lo / t_hi must be INT64_MIN / INT64_MAX and which_mask 0:
+ *     the buckets are the range. inout: row-major [n_groups][n_buckets] mdb_integral_cell; a fresh cell is all-zero
+ *     bytes. A call MERGES into it.
+ *   Rows: those of mdb_grid_batch(in), in that order; no time range applies. Row r has ts(r), v(r) and
+ *     g(r) = group_of_segment[seg(r)] (NULL: 0).
+ *   Linked: rows r and r+1 are linked iff g(r+1) == g(r) and ts(r+1) > ts(r) and ts(r+1) - ts(r) <= max_gap (the
+ *     difference formed as uint64_t after the comparison). The rule holds for every pair of consecutive rows, inside a
+ *     segment and across segments - and, in the list form, across inputs. It does not hold across separate calls: cut
+ *     batches at series boundaries. A regular segment whose sampling interval exceeds max_gap has no linked pair inside
+ *     it. A segment that rebuilds to no row (end_time < start_time) links nothing across it.
+ *   The function: on a linked interval [t0, t1] with values v0, v1, MDB_INTEGRAL_LINEAR is
+ *     f(t) = v0 + (v1 - v0)(t - t0)/(t1 - t0), MDB_INTEGRAL_STEP is f(t) = v0. Outside linked intervals the series is
+ *     undefined and contributes nothing.
+ *   The cell: bucket b is [origin + b*width, origin + (b+1)*width). For every linked interval, a = max(t0, bucket
+ *     start), e = min(t1, bucket end); if e > a, duration += e - a (an integer number of microseconds) and integral +=
+ *     the integral of f over [a, e] in value x microseconds, an f64 formed from integer time differences converted
+ *     once. An interval may cross any number of bucket edges and either of its points may lie outside every bucket;
+ *     nothing overflows for any origin or width.
+ *   Finish: mdb_integral_average writes integral / duration, NaN where duration == 0. mdb_integral_merge_n adds both
+ *     members.
+ *   Exact promises: duration is exact, always - also beside NaN and infinite values; over buckets that cover a group's
+ *     rows the durations sum to the group's linked time. A cell whose contributing values are all one finite c has an
+ *     average within 2^-44 |c| of c. LINEAR: a non-finite v0 or v1 makes the integral of the cells its interval
+ *     touches non-finite; STEP: only a non-finite v0 does.
+ *   Tolerance: |integral - exact| <= 1e-5 x the sum of (e - a) max(|v0|, |v1|) over the cell's pieces.
+ *   Determinism: two runs and the three forms agree bit for bit; no float atomics. The order of segments and
+ *     MDB_AGG_BUCKET_SLICE_PAIRS move integral by rounding only, duration not at all. Moving the origin by a whole
+ *     number of widths, with n_buckets moved along, gives the same bytes.
+ *   Errors (mdb_last_error set, inout untouched; what needs no device is checked before the device is used): a NULL
+ *     argument, width <= 0, n_groups == 0, an overflowing cell count, which_mask != 0, a time range in the bucket
+ *     request, an unknown method, flags != 0, a negative max_gap, a group id >= n_groups on ANY row, the
+ *     malformed-segment classes of mdb_agg_buckets for the segments the request reaches and the neighbour whose first
+ *     point it reads. An empty batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_integral_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                         const mdb_integral_request *request, mdb_integral_cell *inout);
+/* All device pointers: the batch, group_of_segment and inout are in HBM. */
+int mdb_integral_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                             const mdb_integral_request *request, mdb_integral_cell *inout);
+/* Several host batches (rows in the order of the list) folded as one batch: a linked interval may cross from one input
+ * to the next. group_of_segment: one array per batch, or NULL. */
+int mdb_integral_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                              uint32_t n_inputs, const mdb_integral_request *request, mdb_integral_cell *inout);
+/* into[k] += from[k] for k < n, both members. Host memory, no context. */
+int mdb_integral_merge_n(mdb_integral_cell *into, const mdb_integral_cell *from, uint64_t n);
+/* out[k] = cells[k].integral / cells[k].duration, NaN where duration == 0. Host memory, no context. */
+int mdb_integral_average(const mdb_integral_cell *cells, uint64_t n, double *out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -230,6 +230,25 @@ typedef struct mdb_comoments_cell {
     double  c_xy;         /* sum (x - mean_x) * (y - mean_y) */
 } mdb_comoments_cell;      /* 48 bytes */
 
+/* One cell of mdb_integral_buckets*: the series of a bucket and group taken as a function of time. duration: the
+ * microseconds of the bucket on which the function is defined (the clipped linked intervals, mdb.h), exact; integral:
+ * the integral of the function over them, in value * microseconds. The time-weighted average is integral / duration
+ * (mdb_integral_average). A fresh cell is all-zero bytes; cells merge by adding both members. */
+typedef struct mdb_integral_cell {
+    uint64_t duration;
+    double   integral;
+} mdb_integral_cell;       /* 16 bytes */
+
+#define MDB_INTEGRAL_LINEAR 0u   /* trapezoid: the value between two linked points is interpolated */
+#define MDB_INTEGRAL_STEP   1u   /* last observation carried forward */
+
+typedef struct mdb_integral_request {   /* 64 bytes */
+    mdb_bucket_request buckets;  /* t_lo / t_hi must be INT64_MIN / INT64_MAX, which_mask 0: the buckets are the range */
+    int64_t  max_gap;            /* >= 0; INT64_MAX: no gap rule */
+    uint32_t method;             /* MDB_INTEGRAL_* */
+    uint32_t flags;              /* must be 0 */
+} mdb_integral_request;
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -338,5 +357,11 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, mean_y) == 16);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_x) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_y) == 32);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, c_xy) == 40);
+MDB_LAYOUT_ASSERT(sizeof(mdb_integral_cell) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_integral_cell, integral) == 8);
+MDB_LAYOUT_ASSERT(sizeof(mdb_integral_request) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, max_gap) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, method) == 56);
+MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, flags) == 60);
 
 #endif /* MDB_FORMAT_H */

@@ -222,6 +222,27 @@ class EpisodesResultC(C.Structure):
 
 assert C.sizeof(EpisodeC) == 64 and C.sizeof(EpisodesRequestC) == 64
 
+MDB_INTEGRAL_LINEAR = 0
+MDB_INTEGRAL_STEP = 1
+
+
+class IntegralCellC(C.Structure):
+    """mdb_integral_cell: the defined time of a bucket and the integral of the series over it (mdb_integral_buckets*)."""
+    _fields_ = [("duration", C.c_uint64), ("integral", C.c_double)]
+
+
+class IntegralRequestC(C.Structure):
+    """mdb_integral_request: the buckets (no time range, which_mask 0), the gap rule and the interpolation."""
+    _fields_ = [
+        ("buckets", BucketRequestC),
+        ("max_gap", C.c_int64),
+        ("method", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+assert C.sizeof(IntegralCellC) == 16 and C.sizeof(IntegralRequestC) == 64
+
 
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
@@ -373,6 +394,14 @@ _HIP_SYMBOLS = {
                                         C.c_void_p]),
     "mdb_trend_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
                                          C.c_uint32, C.POINTER(BucketRequestC), C.c_void_p]),
+    "mdb_integral_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(IntegralRequestC),
+                                       C.c_void_p]),
+    "mdb_integral_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(IntegralRequestC),
+                                           C.c_void_p]),
+    "mdb_integral_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                            C.c_uint32, C.POINTER(IntegralRequestC), C.c_void_p]),
+    "mdb_integral_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_integral_average": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,

@@ -267,6 +267,44 @@ EPISODE_DTYPE = np.dtype([("first_row", "<u8"), ("count", "<u8"), ("t_first", "<
                           ("min", "<f4"), ("max", "<f4"), ("group", "<u4"), ("first_segment", "<u4"), ("reserved", "<u8")])
 assert EPISODE_DTYPE.itemsize == C.sizeof(_abi.EpisodeC) == 64
 
+# mdb_integral_cell as a numpy record: the cells of mdb_integral_buckets*, row-major [n_groups][n_buckets].
+INTEGRAL_CELL_DTYPE = np.dtype([("duration", "<u8"), ("integral", "<f8")])
+assert INTEGRAL_CELL_DTYPE.itemsize == C.sizeof(_abi.IntegralCellC) == 16
+MDB_INTEGRAL_LINEAR = _abi.MDB_INTEGRAL_LINEAR
+MDB_INTEGRAL_STEP = _abi.MDB_INTEGRAL_STEP
+
+
+def fresh_integral_cells(shape):
+    """Fresh (empty) integral cells: all-zero bytes."""
+    return np.zeros(shape, dtype=INTEGRAL_CELL_DTYPE)
+
+
+def integral_merge(into, from_):
+    """into[k] += from_[k] in place, both members (mdb_integral_merge_n): two arrays of INTEGRAL_CELL_DTYPE of one
+    size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != INTEGRAL_CELL_DTYPE or from_.dtype != INTEGRAL_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("integral_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("integral_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_integral_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def integral_average(cells):
+    """The time-weighted average integral / duration per cell (mdb_integral_average), NaN where duration == 0.
+    Returns float64 of the shape of `cells`."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != INTEGRAL_CELL_DTYPE:
+        raise ValueError("integral_average takes an array of INTEGRAL_CELL_DTYPE")
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if lib.mdb_integral_average(flat.ctypes.data_as(C.c_void_p), flat.size, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
 
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
@@ -1267,6 +1305,87 @@ class Context:
             raise ValueError("the data inside the range spans more than one bucket can hold: use trend_buckets")
         cells = self.trend_buckets(batch, origin, hi - origin + 1, 1, groups, lo, hi, None, n_groups)
         return cells.reshape(n_groups), origin
+
+    # ---- time-weighted averages and integrals: the series as a function of time per bucket --------------------------
+
+    @staticmethod
+    def _integral_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_integral_cells((n_groups, n_buckets))
+        if cells.dtype != INTEGRAL_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of INTEGRAL_CELL_DTYPE")
+        return cells
+
+    @classmethod
+    def _integral_request(cls, origin, width, n_buckets, n_groups, method, max_gap):
+        request = _abi.IntegralRequestC()
+        request.buckets = cls._bucket_request(origin, width, n_buckets, n_groups, None, None, 0)
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.method = int(method)
+        request.flags = 0
+        return request
+
+    def integral_buckets(self, batch, origin, width, n_buckets, groups=None, method=MDB_INTEGRAL_LINEAR, max_gap=None,
+                         cells=None, n_groups=None):
+        """The defined time and the integral of one field per bucket [origin + b * width, origin + (b + 1) * width)
+        and group (mdb_integral_buckets): cells of INTEGRAL_CELL_DTYPE, duration in microseconds, integral in
+        value x microseconds; integral_average gives the time-weighted average. Between two linked rows - same group,
+        time moving forward, at most max_gap apart (None: no gap rule) - the value is interpolated
+        (MDB_INTEGRAL_LINEAR) or the earlier one carried forward (MDB_INTEGRAL_STEP). Returns `cells` (or fresh ones),
+        shape (n_groups, n_buckets), merged in place. `groups` and n_groups as for agg_buckets. Links do not cross
+        calls: cut batches at series boundaries."""
+        return self.integral_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups],
+                                          method, max_gap, cells, n_groups)
+
+    def integral_buckets_list(self, batches, origin, width, n_buckets, groups=None, method=MDB_INTEGRAL_LINEAR,
+                              max_gap=None, cells=None, n_groups=None):
+        """Several host batches merged as one (mdb_integral_buckets_list): a link may cross from one batch to the next;
+        `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._integral_cells(cells, n_groups, n_buckets)
+        request = self._integral_request(origin, width, n_buckets, n_groups, method, max_gap)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_integral_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                       C.byref(request), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def integral_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, method=MDB_INTEGRAL_LINEAR,
+                             max_gap=None, cells=None, n_groups=None):
+        """mdb_integral_buckets_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded
+        again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._integral_cells(cells, n_groups, n_buckets)
+        request = self._integral_request(origin, width, n_buckets, n_groups, method, max_gap)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_integral_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                          None if dev_groups is None else C.c_void_p(dev_groups),
+                                                          C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, INTEGRAL_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def integral(self, batch, groups=None, n_groups=None, method=MDB_INTEGRAL_LINEAR, max_gap=None):
+        """The cells of `batch` as one bucket over its span, one per group (shape (n_groups,)): what a whole-batch
+        time-weighted average or integral needs."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        if len(batch) == 0:
+            return fresh_integral_cells(n_groups)
+        lo = int(min(np.min(batch.start_time), np.min(batch.end_time)))
+        hi = int(max(np.max(batch.start_time), np.max(batch.end_time)))
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the batch spans more than one bucket can hold: use integral_buckets")
+        return self.integral_buckets(batch, lo, hi - lo + 1, 1, groups, method, max_gap, None, n_groups).reshape(n_groups)
 
     # ---- episodes: the maximal runs of points that pass a value predicate ----------------------------------------
 

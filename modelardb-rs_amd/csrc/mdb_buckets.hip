@@ -418,7 +418,7 @@ static int bucket_pieces_entries(mdb_ctx *ctx, const DevSegments &s, const Bucke
 
 int bucket_span_pairs(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const uint32_t *groups,
                       const BucketRequest &r, const unsigned long long **offsets_out, unsigned int **words_out,
-                      unsigned long long *total_out) {
+                      unsigned long long *total_out, const BucketSpanKernel *span_kernel) {
     const uint64_t n = in->n;
     // Span: pair offsets and the read-back words (total pairs, error, unsorted).
     void *p;
@@ -430,7 +430,10 @@ int bucket_span_pairs(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s
     unsigned long long *block_sums = span.take<unsigned long long>(scan_block_sums_bytes(n) / 8);
     unsigned int *words = span.take<unsigned int>(2);
     MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));
-    {
+    if (span_kernel) {
+        LaunchTimer timer(ctx, span_kernel->name);
+        span_kernel->launch(ctx, s, groups, r, counts, words, span_kernel->arg);
+    } else {
         LaunchTimer timer(ctx, "k_agg_bucket_span");
         hipLaunchKernelGGL(k_agg_bucket_span, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, r,
                            counts, words);

@@ -52,12 +52,23 @@ inline uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + BUCKET_THREADS -
 // MDB_AGG_BUCKET_SLICE_PAIRS, or the default: the pairs (and piece entries) of one slice.
 uint64_t slice_pairs_setting();
 
-// k_agg_bucket_span and its scan over the device batch `in` (s = to_dev(in)): *offsets (n + 1, in scratch) are the
-// pair offsets per segment, *words two zeroed read-back words (an error word, an "unsorted" flag) next to them,
-// *total the number of pairs. Fails on a group id that is not below n_groups - on any row.
+// An operator's own span kernel in place of k_agg_bucket_span (mdb_integral.hip: a segment's extent reaches over the
+// link to its right neighbour): launch() enqueues it on the context's stream; it writes counts[i], the pairs of
+// segment i, and ORs ERR_BUCKET_GROUP into *error for a group id that is not below n_groups, as k_agg_bucket_span does.
+struct BucketSpanKernel {
+    const char *name; // (of the launch, for mdb_profile_*)
+    void (*launch)(mdb_ctx *ctx, const DevSegments &s, const uint32_t *groups, const BucketRequest &r,
+                   unsigned long long *counts, unsigned int *error, const void *arg);
+    const void *arg;
+};
+
+// k_agg_bucket_span (span nullptr; or the operator's own) and its scan over the device batch `in` (s = to_dev(in)):
+// *offsets (n + 1, in scratch) are the pair offsets per segment, *words two zeroed read-back words (an error word, an
+// "unsorted" flag) next to them, *total the number of pairs. Fails on a group id that is not below n_groups - on any
+// row.
 int bucket_span_pairs(mdb_ctx *ctx, const mdb_segments *in, const DevSegments &s, const uint32_t *groups,
                       const BucketRequest &r, const unsigned long long **offsets, unsigned int **words,
-                      unsigned long long *total);
+                      unsigned long long *total, const BucketSpanKernel *span = nullptr);
 
 // The entries the pieces of the batch's cursor index will write, one per bucket a piece reaches (offsets: per piece
 // of the index, n_pieces + 1, in scratch).

@@ -102,6 +102,7 @@ enum ScratchSlot {
     SCRATCH_BINNED,              // mdb_binned_buckets*: run counts and offsets per x segment, the scan's sums, the edges' keys
     SCRATCH_EPISODES_SEGMENTS,   // mdb_episodes*: per segment its rows, first row, summary, prefix, counts and the scans
     SCRATCH_EPISODES_OUT,        // ... the episodes of the host forms before they are copied back
+    SCRATCH_INTEGRAL_HEADS,      // mdb_integral_buckets*: the first point's value per segment (the far end of a link)
     SCRATCH_SLOT_COUNT
 };
 

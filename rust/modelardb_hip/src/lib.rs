@@ -35,8 +35,10 @@ pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
     mdb_comoments_cell as ComomentsCell, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
     mdb_episode as Episode, mdb_episodes_request as EpisodesRequest, mdb_moments_cell as MomentsCell,
+    mdb_integral_cell as IntegralCell, mdb_integral_request as IntegralRequest,
     mdb_value_filter as ValueFilter,
 };
+pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
@@ -383,6 +385,21 @@ pub fn comoments_moments(cells: &[ComomentsCell], which: u32) -> Result<Vec<Mome
 pub fn comoments_finish(cells: &[ComomentsCell], kind: u32) -> Result<Vec<f64>> {
     let mut out = vec![0.0f64; cells.len()];
     check(unsafe { sys::mdb_comoments_finish(cells.as_ptr(), cells.len() as u64, kind, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `into[k] += from[k]`, both members: the merge of `mdb_integral_buckets*` (host arithmetic, no GPU).
+pub fn integral_merge(into: &mut [IntegralCell], from: &[IntegralCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_integral_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The time-weighted average `integral / duration` per cell, NaN where `duration == 0` (host arithmetic, no GPU).
+pub fn integral_average(cells: &[IntegralCell]) -> Result<Vec<f64>> {
+    let mut out = vec![0.0f64; cells.len()];
+    check(unsafe { sys::mdb_integral_average(cells.as_ptr(), cells.len() as u64, out.as_mut_ptr()) })?;
     Ok(out)
 }
 
@@ -903,6 +920,55 @@ impl Context {
         check(unsafe {
             sys::mdb_trend_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                         request, cells.as_mut_ptr())
+        })
+    }
+
+    /// Time-weighted averages and integrals: per bucket `[origin + b * width, origin + (b + 1) * width)` and group
+    /// one [`IntegralCell`] - the microseconds on which the series is defined and its integral over them - with the
+    /// value between two linked rows interpolated (`MDB_INTEGRAL_LINEAR`) or carried forward (`MDB_INTEGRAL_STEP`).
+    /// Rows are linked when they share a group, time moves forward and the gap is within `request.max_gap`; the rule
+    /// holds inside a segment and across segments, not across calls: cut batches at series boundaries. `cells` is
+    /// row-major `[n_groups][n_buckets]` (fresh: `IntegralCell::default()`); the batch is merged into it, so
+    /// [`integral_merge`] and [`integral_average`] apply. `request.buckets` takes no time range and `which_mask` 0.
+    pub fn integral_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &IntegralRequest,
+        cells: &mut [IntegralCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.buckets, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_integral_buckets(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::integral_buckets`] for several batches at once (rows in the order of the slice), merged as one
+    /// batch: a linked interval may cross from one batch to the next. `group_of_segment`: `None`, or one entry per
+    /// batch (`None`: that batch's rows in group 0).
+    pub fn integral_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &IntegralRequest,
+        cells: &mut [IntegralCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.buckets, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_integral_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                           request, cells.as_mut_ptr())
         })
     }
 

@@ -319,6 +319,42 @@ pub struct mdb_episodes_result {
 const _: () = assert!(std::mem::size_of::<mdb_episode>() == 64);
 const _: () = assert!(std::mem::size_of::<mdb_episodes_request>() == 64);
 
+/// One cell of `mdb_integral_buckets*`: the microseconds of a bucket on which the series is defined (the clipped
+/// linked intervals) and the integral of the series over them, in value x microseconds. A fresh cell is all-zero bytes
+/// (`Default`); cells merge by adding both members.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_integral_cell {
+    pub duration: u64,
+    pub integral: f64,
+}
+
+/// Trapezoid: the value between two linked points is interpolated.
+pub const MDB_INTEGRAL_LINEAR: u32 = 0;
+/// Last observation carried forward.
+pub const MDB_INTEGRAL_STEP: u32 = 1;
+
+/// The request of `mdb_integral_buckets*`. 64 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_integral_request {
+    /// `t_lo` / `t_hi` must be `i64::MIN` / `i64::MAX` and `which_mask` 0: the buckets are the range.
+    pub buckets: mdb_bucket_request,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// `MDB_INTEGRAL_*`.
+    pub method: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_integral_cell>() == 16);
+const _: () = assert!(std::mem::offset_of!(mdb_integral_cell, integral) == 8);
+const _: () = assert!(std::mem::size_of::<mdb_integral_request>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_integral_request, max_gap) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_integral_request, method) == 56);
+const _: () = assert!(std::mem::offset_of!(mdb_integral_request, flags) == 60);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -507,6 +543,16 @@ unsafe extern "C" {
     pub fn mdb_trend_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
                                   group_of_segment: *const *const u32, n_inputs: u32,
                                   request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
+    // ---- time-weighted averages and integrals per bucket: the series as a function of time (include/mdb.h) ----
+    pub fn mdb_integral_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                request: *const mdb_integral_request, inout: *mut mdb_integral_cell) -> c_int;
+    pub fn mdb_integral_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                    request: *const mdb_integral_request, inout: *mut mdb_integral_cell) -> c_int;
+    pub fn mdb_integral_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                     group_of_segment: *const *const u32, n_inputs: u32,
+                                     request: *const mdb_integral_request, inout: *mut mdb_integral_cell) -> c_int;
+    pub fn mdb_integral_merge_n(into: *mut mdb_integral_cell, from: *const mdb_integral_cell, n: u64) -> c_int;
+    pub fn mdb_integral_average(cells: *const mdb_integral_cell, n: u64, out: *mut f64) -> c_int;
     // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
     pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                                   request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
