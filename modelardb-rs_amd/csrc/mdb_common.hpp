@@ -209,6 +209,7 @@ struct LaunchTimer {
 // deltas so far - so that every piece is decoded by a lane of its own. Not an Arrow column: it belongs to the
 // mdb_segments_owned the library made (mdb_segments_upload, mdb_compress_chunks_dev), is built by the first
 // grid / aggregate call that could use it and dies with the batch.
+struct KeptGridPlan; // (mdb_grid.hip)
 struct MvIndex {
     std::mutex mutex;      // building
     bool built = false;
@@ -258,6 +259,15 @@ struct MvIndex {
     bool chains_built = false;
     void *chain_offsets = nullptr;          // unsigned long long[waves of pieces + 1]
     unsigned long long chains_listed = 0;   // the totals: long << 32 | short
+    // And the plan of a grid call WITHOUT a time range (KeptGridPlan, mdb_grid.hip: descriptors, counts, offsets, the
+    // serial list and the tile map in allocations of its own, about 72 B per segment and 4 B per 4 096 points):
+    // published by the first such call once it has ended without an error, read-only from then on and used by every
+    // later call under the same switches, which then launches the reconstruction kernels only. A call holds the plan
+    // it reads (a copy of the pointer, taken under the mutex) until its kernels are done. MDB_GRID_PLAN_KEEP=0 keeps
+    // none, =<bytes> only plans up to that size.
+    std::shared_ptr<KeptGridPlan> grid_plan;
+    bool grid_plan_refused = false;      // no memory for it, or over the size limit once its size was known: not tried again
+    std::string grid_plan_declined_key;  // the switches under which a plan pointed into a call's scratch: not tried again
     // The index of ONE call over host batches (mv_host_index, mdb_grid.hip): made by host threads while the batches
     // are on their way, for the long streams only - a segment without pieces is the serial kernel's - and living in
     // the context's scratch.

@@ -25,6 +25,8 @@
 //   k_grid_serial    1 lane / segment with a serial dependency, always after k_grid_tiles: MacaqueV
 //                    value streams, residual tails (<= 255 values) and the few irregular timestamp
 //                    streams short enough to live inside their view overwrite the placeholders.
+// A resident batch keeps the plan of its first call without a time range (KeptGridPlan: what the kernels up to
+// k_grid_offsets leave); its later calls begin at k_grid_tiles (MDB_GRID_PLAN_KEEP=0: every call plans).
 // Algorithmic bytes: 73 B/segment read + 12 B/point written (8 B timestamp + 4 B value).
 // The MacaqueV decoders: mdb_mv_pieces.hpp (a lane per piece or per stream), mdb_mv_parallel.hip (many lanes per
 // stream); the cursor index is built here (mv_index_*), the aggregates that read it are mdb_agg_mv.hip.
@@ -2448,7 +2450,121 @@ struct GridPlan {
     uint64_t n_ts_pieces;
     std::shared_ptr<MvIndex> mv_index; // cursors into the batch's MacaqueV streams, if it is a resident batch
     std::shared_ptr<MvIndex> ts_cache_pending; // (grid_plan: the batch's timestamp cursors were copied for later calls)
+    KeptGridPlan *owned = nullptr; // the plan is made in these allocations, not in scratch (grid_plan_keep_begin)
 };
+
+// The plan of a resident batch's grid without a time range, in allocations of its own (MvIndex::grid_plan): what
+// grid_plan and grid_offsets write and the launches of grid_launch_planned only read. The header of the call that
+// made it says what those launches are.
+struct KeptGridPlan {
+    int device = 0;
+    std::string key; // the switches grid_plan reads, as they stood (grid_plan_key)
+    TileDesc *desc = nullptr;
+    uint32_t *counts = nullptr; // one allocation with irregular_totals and irregular_first behind it, as in scratch
+    uint32_t *irregular_totals = nullptr;
+    uint32_t *irregular_first = nullptr;
+    unsigned long long *offsets = nullptr;
+    uint32_t *serial_ids = nullptr;
+    uint32_t *tile_first = nullptr;
+    GridHeader host_header;
+    uint32_t mv_min_values = 0;
+    bool mv_forced = false;
+    bool with_mv_index = false; // the planning call had the batch's cursor index
+    TsCheckpoints checkpoints = {nullptr, nullptr, nullptr, nullptr, nullptr}; // into the batch's kept walk (MvIndex::ts_*), or none
+    uint64_t n_ts_pieces = 0;
+    uint64_t bytes = 0, limit = 0;
+    bool complete = true; // false: a part of the plan lies in the call's scratch after all, it is not published
+    ~KeptGridPlan() {
+        if (!desc && !counts && !offsets && !serial_ids && !tile_first) return;
+        (void)hipSetDevice(device);
+        for (void *allocation : {(void *)desc, (void *)counts, (void *)offsets, (void *)serial_ids, (void *)tile_first})
+            if (allocation) (void)hipFree(allocation);
+    }
+};
+
+// MDB_GRID_PLAN_KEEP: 0 keeps no plan and uses none, a number of bytes keeps the plans up to that size; not set: all.
+static uint64_t grid_plan_keep_limit() {
+    const char *text = option_text("MDB_GRID_PLAN_KEEP");
+    if (!text) return ~0ull;
+    return std::strtoull(text, nullptr, 10);
+}
+
+// The values of the switches grid_plan reads: a kept plan serves the calls made under the ones it was made under.
+static std::string grid_plan_key() {
+    std::string key;
+    for (const char *name : {"MDB_GRID_MV_MIN_VALUES", "MDB_GRID_TS_JUMPS", "MDB_GRID_TS_PIECES", "MDB_GRID_TS_CACHE",
+                             "MDB_GRID_TS_SORT", "MDB_GRID_MV_INDEX", "MDB_GRID_PREPASS_SPLIT"}) {
+        const char *text = option_text(name);
+        key += text ? std::string("=") + text : std::string("-");
+        key += '\n';
+    }
+    return key;
+}
+
+// The batch's kept plan if this call may use it: made under the same switches, on the context's device.
+static std::shared_ptr<KeptGridPlan> grid_plan_kept(mdb_ctx *ctx, const mdb_segments *in) {
+    if (grid_plan_keep_limit() == 0) return nullptr;
+    std::shared_ptr<MvIndex> resident = owned_segments_index(in);
+    if (!resident) return nullptr;
+    std::shared_ptr<KeptGridPlan> kept;
+    {
+        std::lock_guard<std::mutex> lock(resident->mutex);
+        kept = resident->grid_plan;
+    }
+    if (!kept || kept->device != ctx->device || kept->bytes > grid_plan_keep_limit() || kept->key != grid_plan_key()) return nullptr;
+    return kept;
+}
+
+// Before grid_plan: allocations of its own for the plan of a resident batch that has none yet (nullptr: the plan goes
+// to scratch as ever - nothing is kept, the batch is not a resident one, it has a plan already, or an earlier call was
+// refused). The tile map follows in grid_offsets, when the number of points is known.
+static std::shared_ptr<KeptGridPlan> grid_plan_keep_begin(mdb_ctx *ctx, const mdb_segments *in, const std::string &key) {
+    const uint64_t limit = grid_plan_keep_limit();
+    const uint64_t n = in->n;
+    if (limit == 0 || n > 0xfffffff0ull) return nullptr;
+    std::shared_ptr<MvIndex> resident = owned_segments_index(in);
+    if (!resident) return nullptr;
+    const uint64_t bytes = n * sizeof(TileDesc) + 3 * (n + 4) * 4 + (n + 1) * 8 + (n + 1) * 4;
+    {
+        std::lock_guard<std::mutex> lock(resident->mutex);
+        if (resident->grid_plan || resident->grid_plan_refused || resident->grid_plan_declined_key == key) return nullptr;
+    }
+    if (bytes > limit) return nullptr;
+    auto owned = std::make_shared<KeptGridPlan>();
+    owned->device = ctx->device;
+    owned->key = key;
+    owned->bytes = bytes;
+    owned->limit = limit;
+    void *p = nullptr;
+    bool made = hipMalloc(&p, n * sizeof(TileDesc)) == hipSuccess;
+    if (made) owned->desc = static_cast<TileDesc *>(p);
+    made = made && hipMalloc(&p, 3 * (n + 4) * 4) == hipSuccess;
+    if (made) owned->counts = static_cast<uint32_t *>(p);
+    made = made && hipMalloc(&p, (n + 1) * 8) == hipSuccess;
+    if (made) owned->offsets = static_cast<unsigned long long *>(p);
+    made = made && hipMalloc(&p, (n + 1) * 4) == hipSuccess;
+    if (made) owned->serial_ids = static_cast<uint32_t *>(p);
+    if (!made) {
+        (void)hipGetLastError();
+        std::lock_guard<std::mutex> lock(resident->mutex);
+        resident->grid_plan_refused = true;
+        return nullptr;
+    }
+    owned->irregular_totals = owned->counts + n + 4;
+    owned->irregular_first = owned->irregular_totals + n + 4;
+    return owned;
+}
+
+// Where the members of a TsCheckpoints lie in a block of n_pieces slots (scratch, or the one a resident batch keeps).
+static TsCheckpoints ts_checkpoints_in(void *block, const unsigned long long *piece_base, unsigned long long n_pieces, bool jumps) {
+    TsCheckpoints c{piece_base, static_cast<TsCursor *>(block), nullptr, nullptr, nullptr};
+    c.piece_segment = reinterpret_cast<uint2 *>(c.slots + n_pieces);
+    if (jumps) // (n_pieces * 40 bytes in front: 8-byte aligned, which is all a TsJump's members need)
+        c.jumps = reinterpret_cast<TsJump *>(c.piece_segment + n_pieces);
+    if (jumps && n_pieces < 0xffffffffull)
+        c.live = reinterpret_cast<uint32_t *>(c.jumps + n_pieces * TS_JUMPS_PER_PIECE);
+    return c;
+}
 
 // MDB_GRID_MV_MIN_VALUES: "off" disables the parallel MacaqueV decoder, a number sets the stream
 // length from which it is used (tests force it down so that short streams exercise it).
@@ -2716,20 +2832,29 @@ int grid_plan(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan *p
     const uint32_t n_blocks = (uint32_t)((n + SEGS_PER_BLOCK - 1) / SEGS_PER_BLOCK);
     plan->n_blocks = n_blocks;
     void *p;
-    if (scratch_reserve(ctx, SCRATCH_DESC, n * sizeof(TileDesc), &p)) return 1;
-    plan->desc = static_cast<TileDesc *>(p);
-    // counts, then (for segments with irregular timestamps only) their totals and first visible index
-    if (scratch_reserve(ctx, SCRATCH_COUNTS, 3 * (n + 4) * 4, &p)) return 1;
-    plan->counts = static_cast<uint32_t *>(p);
+    if (plan->owned) { // (a resident batch's first plan: straight into the allocations it is kept in)
+        plan->desc = plan->owned->desc;
+        plan->counts = plan->owned->counts;
+        plan->offsets = plan->owned->offsets;
+        plan->serial_ids = plan->owned->serial_ids;
+    } else {
+        if (scratch_reserve(ctx, SCRATCH_DESC, n * sizeof(TileDesc), &p)) return 1;
+        plan->desc = static_cast<TileDesc *>(p);
+        // counts, then (for segments with irregular timestamps only) their totals and first visible index
+        if (scratch_reserve(ctx, SCRATCH_COUNTS, 3 * (n + 4) * 4, &p)) return 1;
+        plan->counts = static_cast<uint32_t *>(p);
+        if (scratch_reserve(ctx, SCRATCH_OFFSETS, (n + 1) * 8, &p)) return 1;
+        plan->offsets = static_cast<unsigned long long *>(p);
+    }
     plan->irregular_totals = plan->counts + n + 4;
     plan->irregular_first = plan->irregular_totals + n + 4;
-    if (scratch_reserve(ctx, SCRATCH_OFFSETS, (n + 1) * 8, &p)) return 1;
-    plan->offsets = static_cast<unsigned long long *>(p);
     if (scratch_reserve(ctx, SCRATCH_BLOCK_SUMS, (uint64_t)(n_blocks + 1) * 16, &p)) return 1;
     plan->block_points = static_cast<unsigned long long *>(p);
     plan->block_serial = plan->block_points + n_blocks + 1;
-    if (scratch_reserve(ctx, SCRATCH_SERIAL_IDS, (n + 1) * 4, &p)) return 1;
-    plan->serial_ids = static_cast<uint32_t *>(p);
+    if (!plan->owned) {
+        if (scratch_reserve(ctx, SCRATCH_SERIAL_IDS, (n + 1) * 4, &p)) return 1;
+        plan->serial_ids = static_cast<uint32_t *>(p);
+    }
     plan->tile_first = nullptr;
     if (scratch_reserve(ctx, SCRATCH_HEADER, sizeof(GridHeader), &p)) return 1;
     plan->header = static_cast<GridHeader *>(p);
@@ -2756,13 +2881,7 @@ int grid_plan(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan *p
     const char *jumps_setting = option_text("MDB_GRID_TS_JUMPS");
     const bool jumps = !range.enabled && !(jumps_setting && std::strcmp(jumps_setting, "0") == 0);
     auto point_checkpoints_into = [&](void *block, unsigned long long *piece_base, unsigned long long n_pieces) {
-        plan->checkpoints.piece_base = piece_base;
-        plan->checkpoints.slots = static_cast<TsCursor *>(block);
-        plan->checkpoints.piece_segment = reinterpret_cast<uint2 *>(plan->checkpoints.slots + n_pieces);
-        if (jumps) // (n_pieces * 40 bytes in front: 8-byte aligned, which is all a TsJump's members need)
-            plan->checkpoints.jumps = reinterpret_cast<TsJump *>(plan->checkpoints.piece_segment + n_pieces);
-        if (jumps && n_pieces < 0xffffffffull)
-            plan->checkpoints.live = reinterpret_cast<uint32_t *>(plan->checkpoints.jumps + n_pieces * TS_JUMPS_PER_PIECE);
+        plan->checkpoints = ts_checkpoints_in(block, piece_base, n_pieces, jumps);
         plan->n_ts_pieces = n_pieces;
     };
     const uint64_t per_piece = sizeof(TsCursor) + sizeof(uint2) + (jumps ? TS_JUMPS_PER_PIECE * sizeof(TsJump) + 4 : 0);
@@ -2892,8 +3011,22 @@ int grid_plan(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan *p
 // Output offsets, serial work list, rows-per-segment and the tile map for the planned batch.
 int grid_offsets(mdb_ctx *ctx, const mdb_segments *in, uint32_t *rows_per_segment, GridPlan *plan) {
     const uint64_t total = plan->host_header.total_points;
-    void *p;
-    if (scratch_reserve(ctx, SCRATCH_TILE_MAP, ((total + TILE_POINTS - 1) / TILE_POINTS + 2) * 4, &p)) return 1;
+    void *p = nullptr;
+    const uint64_t map_bytes = ((total + TILE_POINTS - 1) / TILE_POINTS + 2) * 4;
+    if (KeptGridPlan *owned = plan->owned) {
+        // (over the size limit with the map, or no memory for it: the map in scratch, and the plan is not kept)
+        if (owned->bytes + map_bytes > owned->limit) {
+            owned->complete = false;
+        } else if (hipMalloc(&p, map_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            owned->complete = false;
+            p = nullptr;
+        } else {
+            owned->tile_first = static_cast<uint32_t *>(p);
+            owned->bytes += map_bytes;
+        }
+    }
+    if (!p && scratch_reserve(ctx, SCRATCH_TILE_MAP, map_bytes, &p)) return 1;
     plan->tile_first = static_cast<uint32_t *>(p);
     if (in->n == 0) return 0;
     LaunchTimer timer(ctx, "k_grid_offsets");
@@ -3038,10 +3171,25 @@ int grid_launch_streams(mdb_ctx *ctx, const DevSegments &s, TimeRange range, Gri
 }
 
 // Launch the reconstruction of a planned batch into device buffers (enqueue + final error check).
+static int grid_launch_planned(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan &plan, int64_t *out_ts, float *out_val);
+
 int grid_launch(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan &plan, int64_t *out_ts,
                 float *out_val, uint32_t *out_rows) {
-    const uint64_t total = plan.host_header.total_points;
     if (grid_offsets(ctx, in, out_rows, &plan)) return 1;
+    return grid_launch_planned(ctx, in, range, plan, out_ts, out_val);
+}
+
+// rows_per_segment of a call on a kept plan: the low 31 bits of its counts (what k_grid_offsets writes on a planning call).
+__global__ __launch_bounds__(256) void k_grid_rows(const uint32_t *__restrict__ counts, uint64_t n,
+                                                   uint32_t *__restrict__ rows_per_segment) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) rows_per_segment[i] = counts[i] & COUNT_MASK;
+}
+
+// The launches behind a complete plan (offsets, serial list and tile map made, by this call or kept): they read the
+// plan's arrays and write the output and the header's error word.
+static int grid_launch_planned(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, GridPlan &plan, int64_t *out_ts, float *out_val) {
+    const uint64_t total = plan.host_header.total_points;
     if (total == 0) return 0;
     if (!out_val) return fail("out_val must not be NULL.");
     if ((reinterpret_cast<uintptr_t>(out_ts) & 15u) || (reinterpret_cast<uintptr_t>(out_val) & 15u))
@@ -3190,6 +3338,76 @@ int grid_fused(mdb_ctx *ctx, const mdb_segments *in, int64_t *out_ts, float *out
     return 0;
 }
 
+// A call on the plan its batch keeps: no index building, no prepass, no scans, no read-back of a header - the
+// launches behind the plan, and the synchronisation and the look at the error word that end every grid call.
+static int grid_from_kept_plan(mdb_ctx *ctx, const mdb_segments *in, const KeptGridPlan &kept, GridPlan &plan, int64_t *out_ts,
+                               float *out_val, uint32_t *out_rows, uint64_t cap, uint64_t *n_out, mdb_grid_metrics *metrics) {
+    const uint64_t total = kept.host_header.total_points;
+    if (n_out) *n_out = total;
+    fill_metrics(kept.host_header, metrics);
+    if (total > cap)
+        return fail("Output buffers too small: " + std::to_string(total) + " data points but capacity " +
+                    std::to_string(cap) + ".");
+    void *p = nullptr;
+    if (scratch_reserve(ctx, SCRATCH_HEADER, sizeof(GridHeader), &p)) return 1;
+    plan.header = static_cast<GridHeader *>(p); // (the call's own: the launches write its error word)
+    plan.host_header = kept.host_header;        // (error == 0, or the plan would not have been published)
+    MDB_HIP_CHECK(hipMemcpyAsync(plan.header, &kept.host_header, sizeof(GridHeader), hipMemcpyHostToDevice, ctx->stream));
+    plan.desc = kept.desc;
+    plan.counts = kept.counts;
+    plan.irregular_totals = kept.irregular_totals;
+    plan.irregular_first = kept.irregular_first;
+    plan.offsets = kept.offsets;
+    plan.serial_ids = kept.serial_ids;
+    plan.tile_first = kept.tile_first;
+    plan.block_points = plan.block_serial = nullptr;
+    plan.n_blocks = (uint32_t)((in->n + SEGS_PER_BLOCK - 1) / SEGS_PER_BLOCK);
+    plan.mv_min_values = kept.mv_min_values;
+    plan.mv_forced = kept.mv_forced;
+    plan.checkpoints = kept.checkpoints;
+    plan.n_ts_pieces = kept.n_ts_pieces;
+    if (kept.with_mv_index) plan.mv_index = owned_segments_index(in); // (built and found usable by the planning call)
+    if (out_rows) {
+        LaunchTimer timer(ctx, "k_grid_rows");
+        hipLaunchKernelGGL(k_grid_rows, dim3((uint32_t)((in->n + 255) / 256)), dim3(256), 0, ctx->stream, kept.counts,
+                           (uint64_t)in->n, out_rows);
+    }
+    if (grid_launch_planned(ctx, in, TimeRange{0, 0, 0}, plan, out_ts, out_val)) return 1;
+    return grid_late_error(ctx, plan);
+}
+
+// After the call's last synchronisation, without an error: the plan made in `owned` becomes the batch's, unless another
+// call has published one meanwhile (this one's is then freed with `owned`) or it points at something of this call's.
+static void grid_plan_keep_publish(const mdb_segments *in, const GridPlan &plan, const std::shared_ptr<KeptGridPlan> &owned) {
+    if (plan.host_header.error) return;
+    std::shared_ptr<MvIndex> resident = owned_segments_index(in);
+    if (!resident) return;
+    std::lock_guard<std::mutex> lock(resident->mutex);
+    if (!owned->complete) {
+        resident->grid_plan_refused = true;
+        return;
+    }
+    if (resident->grid_plan) return;
+    if (plan.mv_index && plan.mv_index != resident) return; // (cursors of one call's own)
+    if (plan.checkpoints.piece_base) {
+        // Checkpoints of the timestamp streams: the kept walk's (this call's copy of them, made behind its walk, or an
+        // earlier call's) serve every later call; a walk that only lies in scratch does not outlive this one.
+        const bool jumps = plan.checkpoints.jumps != nullptr;
+        if (!resident->ts_built || resident->ts_jumps != jumps || resident->ts_n_pieces != plan.n_ts_pieces || !resident->ts_slots) {
+            resident->grid_plan_declined_key = owned->key;
+            return;
+        }
+        owned->checkpoints = ts_checkpoints_in(resident->ts_slots, static_cast<const unsigned long long *>(resident->ts_piece_base),
+                                               resident->ts_n_pieces, jumps);
+        owned->n_ts_pieces = plan.n_ts_pieces;
+    }
+    owned->host_header = plan.host_header;
+    owned->mv_min_values = plan.mv_min_values;
+    owned->mv_forced = plan.mv_forced;
+    owned->with_mv_index = plan.mv_index != nullptr;
+    resident->grid_plan = owned;
+}
+
 int grid_batch_dev_locked(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, int64_t *out_ts,
                           float *out_val, uint32_t *out_rows, uint64_t cap, uint64_t *n_out,
                           mdb_grid_metrics *metrics) {
@@ -3199,8 +3417,23 @@ int grid_batch_dev_locked(mdb_ctx *ctx, const mdb_segments *in, TimeRange range,
         if (done) return 0;
     }
     GridPlan plan;
+    if (!range.enabled)
+        if (std::shared_ptr<KeptGridPlan> kept = grid_plan_kept(ctx, in))
+            return grid_from_kept_plan(ctx, in, *kept, plan, out_ts, out_val, out_rows, cap, n_out, metrics);
     std::shared_ptr<MvIndex> index;
     if (mv_index_prepare(ctx, in, &index)) return 1;
+    // (a resident batch's first call without a range plans into allocations of its own, to be kept if all goes well;
+    // `owned` outlives the call's last synchronisation below: nothing of it is freed under a running kernel)
+    std::shared_ptr<KeptGridPlan> owned;
+    if (!range.enabled) owned = grid_plan_keep_begin(ctx, in, grid_plan_key());
+    plan.owned = owned.get();
+    struct SyncOnTheWayOut { // (an error return with kernels still reading `owned`: destroyed before it)
+        mdb_ctx *ctx;
+        bool armed;
+        ~SyncOnTheWayOut() {
+            if (armed) (void)hipStreamSynchronize(ctx->stream);
+        }
+    } sync_on_the_way_out{ctx, owned != nullptr};
     if (grid_plan(ctx, in, range, &plan)) return 1;
     plan.mv_index = index;
     const uint64_t total = plan.host_header.total_points;
@@ -3210,7 +3443,10 @@ int grid_batch_dev_locked(mdb_ctx *ctx, const mdb_segments *in, TimeRange range,
         return fail("Output buffers too small: " + std::to_string(total) + " data points but capacity " +
                     std::to_string(cap) + ".");
     if (grid_launch(ctx, in, range, plan, out_ts, out_val, out_rows)) return 1;
-    return grid_late_error(ctx, plan);
+    if (grid_late_error(ctx, plan)) return 1;
+    sync_on_the_way_out.armed = false;
+    if (owned) grid_plan_keep_publish(in, plan, owned);
+    return 0;
 }
 
 int grid_range_plan(mdb_ctx *ctx, const mdb_segments *in, int64_t t_lo, int64_t t_hi, uint64_t *total,
@@ -3256,6 +3492,11 @@ namespace {
 const TimeRange NO_RANGE = {0, 0, 0};
 
 int grid_count_dev_locked(mdb_ctx *ctx, const mdb_segments *in, TimeRange range, uint64_t *n_out) {
+    if (!range.enabled) // (a resident batch with a kept plan: its header has the answer; counting builds none)
+        if (std::shared_ptr<KeptGridPlan> kept = grid_plan_kept(ctx, in)) {
+            *n_out = kept->host_header.total_points;
+            return 0;
+        }
     GridPlan plan;
     if (grid_plan(ctx, in, range, &plan)) return 1;
     *n_out = plan.host_header.total_points;
