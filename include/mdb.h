@@ -880,6 +880,59 @@ int mdb_integral_merge_n(mdb_integral_cell *into, const mdb_integral_cell *from,
 /* out[k] = cells[k].integral / cells[k].duration, NaN where duration == 0. Host memory, no context. */
 int mdb_integral_average(const mdb_integral_cell *cells, uint64_t n, double *out);
 
+/* Extension: the value of a series AT REGULAR INSTANTS - gap-fill, last observation carried forward, interpolation.
+ * Elsewhere time_bucket_gapfill(...) with locf() / interpolate(), or resample().ffill() / .interpolate(); it is also
+ * how two fields that do not share timestamps are brought to one time axis. Here a PMC-Mean or Swing segment on regular
+ * timestamps gives the value at any instant inside it in O(1), one lane per (segment, instant), and 16 bytes per
+ * instant leave the device however many points lie between two instants.
+ *   request: mdb_sample_request (mdb_format.h). Instant k is origin + k*width for k < n_buckets. instants.t_lo / t_hi
+ *     must be INT64_MIN / INT64_MAX and which_mask 0. inout: row-major [n_groups][n_instants] mdb_sample_cell; a fresh
+ *     cell is all-zero bytes. A call MERGES into it.
+ *   Rows: those of mdb_grid_batch(in), in that order. Row r has ts(r), v(r) and g(r) = group_of_segment[seg(r)]
+ *     (NULL: 0).
+ *   Linked: exactly the rule of mdb_integral_buckets - rows r and r+1 are linked iff g(r+1) == g(r) and ts(r+1) > ts(r)
+ *     and ts(r+1) - ts(r) <= max_gap; inside segments, across segments, across the inputs of the list form; not across
+ *     calls.
+ *   Contributions at instant T, to cell (group, k):
+ *     (a) every row with ts(r) == T contributes v(r);
+ *     (b) under MDB_SAMPLE_LINEAR and MDB_SAMPLE_STEP every linked interval (t0, v0) - (t1, v1) with t0 < T < t1
+ *         contributes f(T): STEP f = v0; LINEAR f = v0 when v0 == v1, else
+ *         (double)v0 + ((double)v1 - (double)v0) * ((double)(T - t0) / (double)(t1 - t0)), the time differences formed
+ *         in uint64_t and converted once. MDB_SAMPLE_EXACT has no (b).
+ *     Each contribution adds 1 to count and its value, as f64, to sum. An instant nothing reaches keeps its cell
+ *     untouched: that is the gap of gap-fill.
+ *   Finish: mdb_sample_values writes sum / count, NaN where count == 0. mdb_sample_merge_n merges cells.
+ *   Exact promises: count is exact, always - also beside NaN and infinite values. A cell with count == 1 holds sum ==
+ *     that one contribution bit for bit (a cell that has received nothing takes its first contribution whole), so one
+ *     series sampled on its own grid gives the float of mdb_grid_batch exactly under all three methods. A contribution
+ *     that reads a non-finite value makes sum non-finite: LINEAR reads v0 or v1, STEP and rows read v0.
+ *   Tolerance: |sum - exact| <= 2^-48 x the sum of max(|v0|, |v1|) over the cell's contributions: one contribution
+ *     carries four roundings of at most 2^-53 on magnitudes up to 2 max(|v0|, |v1|), each addition of a cell 2^-53 of
+ *     the running sum; the rest is margin for contraction and the order of additions.
+ *   Determinism: two runs and the three forms agree bit for bit; no float atomics. MDB_AGG_BUCKET_SLICE_PAIRS and the
+ *     order of segments move sum by rounding only, and only in cells with count > 1; count never moves. Moving the
+ *     origin by a whole number of widths, with n_buckets moved along, gives the same bytes. Nothing overflows for any
+ *     origin, width or timestamp; instants a real timestamp cannot reach are never formed.
+ *   Errors (mdb_last_error set, inout untouched; what needs no device is checked before the device is used): a NULL
+ *     argument, width <= 0, n_groups == 0, an overflowing cell count, which_mask != 0, a time range in the request, an
+ *     unknown method, flags != 0, a negative max_gap, a group id >= n_groups on ANY row, the malformed-segment classes
+ *     of mdb_agg_buckets for the segments the request reaches and the neighbour whose first point it reads. An empty
+ *     batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_sample_at(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                  const mdb_sample_request *request, mdb_sample_cell *inout);
+/* All device pointers: the batch, group_of_segment and inout are in HBM. */
+int mdb_sample_at_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                      const mdb_sample_request *request, mdb_sample_cell *inout);
+/* Several host batches (rows in the order of the list) sampled as one batch: a linked interval may cross from one
+ * input to the next. group_of_segment: one array per batch, or NULL. */
+int mdb_sample_at_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                       uint32_t n_inputs, const mdb_sample_request *request, mdb_sample_cell *inout);
+/* into[k] merged with from[k] for k < n: a cell with count == 0 takes the other whole, else both members are added.
+ * Host memory, no context. */
+int mdb_sample_merge_n(mdb_sample_cell *into, const mdb_sample_cell *from, uint64_t n);
+/* out[k] = cells[k].sum / cells[k].count, NaN where count == 0. Host memory, no context. */
+int mdb_sample_values(const mdb_sample_cell *cells, uint64_t n, double *out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

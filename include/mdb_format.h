@@ -249,6 +249,26 @@ typedef struct mdb_integral_request {   /* 64 bytes */
     uint32_t flags;              /* must be 0 */
 } mdb_integral_request;
 
+/* One cell of mdb_sample_at*: the value of the series of a group at one instant. count: the contributions the instant
+ * received (rows on it, linked intervals around it, mdb.h), exact; sum: their values added as f64. The sampled value
+ * is sum / count (mdb_sample_values). A fresh cell is all-zero bytes; a cell that has received nothing takes the other
+ * whole when two merge, else both members are added. */
+typedef struct mdb_sample_cell {
+    uint64_t count;
+    double   sum;
+} mdb_sample_cell;         /* 16 bytes */
+
+#define MDB_SAMPLE_LINEAR 0u   /* interpolate between two linked rows */
+#define MDB_SAMPLE_STEP   1u   /* last observation carried forward over a linked interval */
+#define MDB_SAMPLE_EXACT  2u   /* only rows that lie on an instant; nothing between rows */
+
+typedef struct mdb_sample_request {     /* 64 bytes, laid out like mdb_integral_request */
+    mdb_bucket_request instants; /* instant k is origin + k*width, k < n_buckets; t_lo / t_hi INT64_MIN / INT64_MAX, which_mask 0 */
+    int64_t  max_gap;            /* >= 0; INT64_MAX: no gap rule */
+    uint32_t method;             /* MDB_SAMPLE_* */
+    uint32_t flags;              /* must be 0 */
+} mdb_sample_request;
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -363,5 +383,13 @@ MDB_LAYOUT_ASSERT(sizeof(mdb_integral_request) == 64);
 MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, max_gap) == 48);
 MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, method) == 56);
 MDB_LAYOUT_ASSERT(offsetof(mdb_integral_request, flags) == 60);
+MDB_LAYOUT_ASSERT(sizeof(mdb_sample_cell) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_cell, count) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_cell, sum) == 8);
+MDB_LAYOUT_ASSERT(sizeof(mdb_sample_request) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, instants) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, max_gap) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, method) == 56);
+MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, flags) == 60);
 
 #endif /* MDB_FORMAT_H */

@@ -243,6 +243,28 @@ class IntegralRequestC(C.Structure):
 
 assert C.sizeof(IntegralCellC) == 16 and C.sizeof(IntegralRequestC) == 64
 
+MDB_SAMPLE_LINEAR = 0
+MDB_SAMPLE_STEP = 1
+MDB_SAMPLE_EXACT = 2
+
+
+class SampleCellC(C.Structure):
+    """mdb_sample_cell: the contributions an instant received and their f64 sum (mdb_sample_at*)."""
+    _fields_ = [("count", C.c_uint64), ("sum", C.c_double)]
+
+
+class SampleRequestC(C.Structure):
+    """mdb_sample_request: the instants (no time range, which_mask 0), the gap rule and the method."""
+    _fields_ = [
+        ("instants", BucketRequestC),
+        ("max_gap", C.c_int64),
+        ("method", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+assert C.sizeof(SampleCellC) == 16 and C.sizeof(SampleRequestC) == 64
+
 
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
@@ -402,6 +424,13 @@ _HIP_SYMBOLS = {
                                             C.c_uint32, C.POINTER(IntegralRequestC), C.c_void_p]),
     "mdb_integral_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_integral_average": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mdb_sample_at": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(SampleRequestC), C.c_void_p]),
+    "mdb_sample_at_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(SampleRequestC),
+                                    C.c_void_p]),
+    "mdb_sample_at_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                     C.POINTER(SampleRequestC), C.c_void_p]),
+    "mdb_sample_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_sample_values": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,

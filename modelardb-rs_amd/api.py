@@ -306,6 +306,47 @@ def integral_average(cells):
     return out.reshape(cells.shape)
 
 
+
+# mdb_sample_cell as a numpy record: the cells of mdb_sample_at*, row-major [n_groups][n_instants].
+SAMPLE_CELL_DTYPE = np.dtype([("count", "<u8"), ("sum", "<f8")])
+assert SAMPLE_CELL_DTYPE.itemsize == C.sizeof(_abi.SampleCellC) == 16
+MDB_SAMPLE_LINEAR = _abi.MDB_SAMPLE_LINEAR
+MDB_SAMPLE_STEP = _abi.MDB_SAMPLE_STEP
+MDB_SAMPLE_EXACT = _abi.MDB_SAMPLE_EXACT
+
+
+def fresh_sample_cells(shape):
+    """Fresh (empty) sample cells: all-zero bytes."""
+    return np.zeros(shape, dtype=SAMPLE_CELL_DTYPE)
+
+
+def sample_merge(into, from_):
+    """into[k] merged with from_[k] in place (mdb_sample_merge_n): a cell with count == 0 takes the other whole, else
+    both members are added. Two arrays of SAMPLE_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != SAMPLE_CELL_DTYPE or from_.dtype != SAMPLE_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("sample_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("sample_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_sample_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def sample_values(cells):
+    """The sampled value sum / count per cell (mdb_sample_values), NaN where count == 0: the gaps of gap-fill.
+    Returns float64 of the shape of `cells`."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != SAMPLE_CELL_DTYPE:
+        raise ValueError("sample_values takes an array of SAMPLE_CELL_DTYPE")
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if lib.mdb_sample_values(flat.ctypes.data_as(C.c_void_p), flat.size, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -1386,6 +1427,74 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the batch spans more than one bucket can hold: use integral_buckets")
         return self.integral_buckets(batch, lo, hi - lo + 1, 1, groups, method, max_gap, None, n_groups).reshape(n_groups)
+
+    # ---- sampling: the value of a series at regular instants (gap-fill, LOCF, interpolation) --------------------
+
+    @staticmethod
+    def _sample_cells(cells, n_groups, n_instants):
+        if cells is None:
+            return fresh_sample_cells((n_groups, n_instants))
+        if cells.dtype != SAMPLE_CELL_DTYPE or cells.shape != (n_groups, n_instants) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_instants}) array of SAMPLE_CELL_DTYPE")
+        return cells
+
+    @classmethod
+    def _sample_request(cls, origin, width, n_instants, n_groups, method, max_gap):
+        request = _abi.SampleRequestC()
+        request.instants = cls._bucket_request(origin, width, n_instants, n_groups, None, None, 0)
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.method = int(method)
+        request.flags = 0
+        return request
+
+    def sample_at(self, batch, origin, width, n_instants, groups=None, method=MDB_SAMPLE_LINEAR, max_gap=None,
+                  cells=None, n_groups=None):
+        """The value of one field at the instants origin + k * width, k < n_instants, per group (mdb_sample_at): cells
+        of SAMPLE_CELL_DTYPE; sample_values gives sum / count, NaN where nothing reaches an instant. A row on an
+        instant contributes its value; between two linked rows - same group, time moving forward, at most max_gap
+        apart (None: no gap rule) - the value is interpolated (MDB_SAMPLE_LINEAR) or the earlier one carried forward
+        (MDB_SAMPLE_STEP); MDB_SAMPLE_EXACT takes rows only. Returns `cells` (or fresh ones), shape (n_groups,
+        n_instants), merged in place. `groups` and n_groups as for agg_buckets. Links do not cross calls: cut batches
+        at series boundaries."""
+        return self.sample_at_list([batch], origin, width, n_instants, None if groups is None else [groups], method,
+                                   max_gap, cells, n_groups)
+
+    def sample_at_list(self, batches, origin, width, n_instants, groups=None, method=MDB_SAMPLE_LINEAR, max_gap=None,
+                       cells=None, n_groups=None):
+        """Several host batches sampled as one (mdb_sample_at_list): a link may cross from one batch to the next;
+        `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._sample_cells(cells, n_groups, n_instants)
+        request = self._sample_request(origin, width, n_instants, n_groups, method, max_gap)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_sample_at_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def sample_at_dev(self, dev_segments, origin, width, n_instants, groups=None, method=MDB_SAMPLE_LINEAR,
+                      max_gap=None, cells=None, n_groups=None):
+        """mdb_sample_at_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._sample_cells(cells, n_groups, n_instants)
+        request = self._sample_request(origin, width, n_instants, n_groups, method, max_gap)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_sample_at_dev(self.handle, C.byref(dev_segments.seg),
+                                                   None if dev_groups is None else C.c_void_p(dev_groups),
+                                                   C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, SAMPLE_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
 
     # ---- episodes: the maximal runs of points that pass a value predicate ----------------------------------------
 

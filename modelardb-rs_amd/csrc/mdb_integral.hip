@@ -164,6 +164,13 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_integral_fold(IntegralTree t
     cells[key] = cell;
 }
 
+void integral_heads_launch(mdb_ctx *ctx, const DevSegments &s, const uint32_t *groups, const unsigned long long *offsets,
+                           IntegralHead *heads, unsigned int *error) {
+    LaunchTimer timer(ctx, "k_integral_heads");
+    hipLaunchKernelGGL(k_integral_heads, dim3(blocks_for(s.n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, offsets,
+                       heads, error);
+}
+
 static void integral_span_launch(mdb_ctx *ctx, const DevSegments &s, const uint32_t *groups, const BucketRequest &,
                                  unsigned long long *counts, unsigned int *error, const void *arg) {
     hipLaunchKernelGGL(k_integral_span, dim3(blocks_for(s.n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups,
@@ -221,11 +228,7 @@ static int integral_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *gr
     const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
 
     // (the words are zero: bucket_span_pairs left them so; the heads' errors are read back with the first slice's)
-    {
-        LaunchTimer timer(ctx, "k_integral_heads");
-        hipLaunchKernelGGL(k_integral_heads, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, offsets,
-                           heads, words);
-    }
+    integral_heads_launch(ctx, s, groups, offsets, heads, words);
     for (uint64_t k = 0; k < n_slices; k++) {
         const uint64_t p0 = k * slice, p1 = std::min<uint64_t>(p0 + slice, total), m = p1 - p0;
         if (k > 0) MDB_HIP_CHECK(hipMemsetAsync(words, 0, 8, ctx->stream));

@@ -249,6 +249,12 @@ struct IntegralHead { // the first row of a segment, as its left neighbour's lin
     uint32_t rows; // 0: the segment rebuilds to no row
 };
 
+// mdb_integral.hip: k_integral_heads enqueued on the context's stream - heads[i] for every segment i > 0 whose left
+// neighbour has pairs (offsets) and shares its group; the segments' errors are ORed into *error. Shared with
+// mdb_sample.hip, whose links read the same heads.
+void integral_heads_launch(mdb_ctx *ctx, const DevSegments &s, const uint32_t *groups, const unsigned long long *offsets,
+                           IntegralHead *heads, unsigned int *error);
+
 __device__ __forceinline__ bool integral_same_group(const uint32_t *groups, uint64_t i, uint64_t j) {
     return !groups || groups[i] == groups[j];
 }

@@ -36,9 +36,11 @@ pub use sys::{
     mdb_comoments_cell as ComomentsCell, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
     mdb_episode as Episode, mdb_episodes_request as EpisodesRequest, mdb_moments_cell as MomentsCell,
     mdb_integral_cell as IntegralCell, mdb_integral_request as IntegralRequest,
+    mdb_sample_cell as SampleCell, mdb_sample_request as SampleRequest,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
+pub use sys::{MDB_SAMPLE_EXACT, MDB_SAMPLE_LINEAR, MDB_SAMPLE_STEP};
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
@@ -394,6 +396,22 @@ pub fn integral_merge(into: &mut [IntegralCell], from: &[IntegralCell]) -> Resul
         return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
     }
     check(unsafe { sys::mdb_integral_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// `into[k]` merged with `from[k]`: a cell with `count == 0` takes the other whole, else both members are added - the
+/// merge of `mdb_sample_at*` (host arithmetic, no GPU).
+pub fn sample_merge(into: &mut [SampleCell], from: &[SampleCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_sample_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The sampled value `sum / count` per cell, NaN where `count == 0`: the gaps of gap-fill (host arithmetic, no GPU).
+pub fn sample_values(cells: &[SampleCell]) -> Result<Vec<f64>> {
+    let mut out = vec![0.0f64; cells.len()];
+    check(unsafe { sys::mdb_sample_values(cells.as_ptr(), cells.len() as u64, out.as_mut_ptr()) })?;
+    Ok(out)
 }
 
 /// The time-weighted average `integral / duration` per cell, NaN where `duration == 0` (host arithmetic, no GPU).
@@ -969,6 +987,54 @@ impl Context {
         check(unsafe {
             sys::mdb_integral_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                            request, cells.as_mut_ptr())
+        })
+    }
+
+    /// The value of a series at the instants `origin + k * width`, `k < n_buckets`: per instant and group one
+    /// [`SampleCell`]. A row on an instant contributes its value; between two linked rows the value is interpolated
+    /// (`MDB_SAMPLE_LINEAR`) or the earlier one carried forward (`MDB_SAMPLE_STEP`); `MDB_SAMPLE_EXACT` takes rows
+    /// only. Rows are linked as for [`Context::integral_buckets`]. `cells` is row-major `[n_groups][n_instants]`
+    /// (fresh: `SampleCell::default()`); the batch is merged into it, so [`sample_merge`] and [`sample_values`] apply.
+    /// `request.instants` takes no time range and `which_mask` 0.
+    pub fn sample_at(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &SampleRequest,
+        cells: &mut [SampleCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.instants, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_sample_at(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::sample_at`] for several batches at once (rows in the order of the slice), sampled as one batch: a
+    /// linked interval may cross from one batch to the next. `group_of_segment`: `None`, or one entry per batch
+    /// (`None`: that batch's rows in group 0).
+    pub fn sample_at_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &SampleRequest,
+        cells: &mut [SampleCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.instants, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_sample_at_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32, request,
+                                    cells.as_mut_ptr())
         })
     }
 

@@ -355,6 +355,47 @@ const _: () = assert!(std::mem::offset_of!(mdb_integral_request, max_gap) == 48)
 const _: () = assert!(std::mem::offset_of!(mdb_integral_request, method) == 56);
 const _: () = assert!(std::mem::offset_of!(mdb_integral_request, flags) == 60);
 
+/// One cell of `mdb_sample_at*`: the contributions an instant received (rows on it, linked intervals around it) and
+/// their values added as f64; the sampled value is `sum / count`. A fresh cell is all-zero bytes (`Default`); a cell
+/// with `count == 0` takes the other whole when two merge, else both members are added.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_sample_cell {
+    pub count: u64,
+    pub sum: f64,
+}
+
+/// Interpolate between two linked rows.
+pub const MDB_SAMPLE_LINEAR: u32 = 0;
+/// Last observation carried forward over a linked interval.
+pub const MDB_SAMPLE_STEP: u32 = 1;
+/// Only rows that lie on an instant; nothing between rows.
+pub const MDB_SAMPLE_EXACT: u32 = 2;
+
+/// The request of `mdb_sample_at*`. 64 bytes, laid out like `mdb_integral_request`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_sample_request {
+    /// Instant k is `origin + k * width`, `k < n_buckets`; `t_lo` / `t_hi` must be `i64::MIN` / `i64::MAX` and
+    /// `which_mask` 0.
+    pub instants: mdb_bucket_request,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// `MDB_SAMPLE_*`.
+    pub method: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_sample_cell>() == 16);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_cell, count) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_cell, sum) == 8);
+const _: () = assert!(std::mem::size_of::<mdb_sample_request>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_request, instants) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_request, max_gap) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_request, method) == 56);
+const _: () = assert!(std::mem::offset_of!(mdb_sample_request, flags) == 60);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -553,6 +594,17 @@ unsafe extern "C" {
                                      request: *const mdb_integral_request, inout: *mut mdb_integral_cell) -> c_int;
     pub fn mdb_integral_merge_n(into: *mut mdb_integral_cell, from: *const mdb_integral_cell, n: u64) -> c_int;
     pub fn mdb_integral_average(cells: *const mdb_integral_cell, n: u64, out: *mut f64) -> c_int;
+
+    // ---- the value of a series at regular instants: gap-fill, LOCF, interpolation (include/mdb.h) ----
+    pub fn mdb_sample_at(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                         request: *const mdb_sample_request, inout: *mut mdb_sample_cell) -> c_int;
+    pub fn mdb_sample_at_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                             request: *const mdb_sample_request, inout: *mut mdb_sample_cell) -> c_int;
+    pub fn mdb_sample_at_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                              group_of_segment: *const *const u32, n_inputs: u32,
+                              request: *const mdb_sample_request, inout: *mut mdb_sample_cell) -> c_int;
+    pub fn mdb_sample_merge_n(into: *mut mdb_sample_cell, from: *const mdb_sample_cell, n: u64) -> c_int;
+    pub fn mdb_sample_values(cells: *const mdb_sample_cell, n: u64, out: *mut f64) -> c_int;
     // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
     pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                                   request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
