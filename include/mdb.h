@@ -933,6 +933,65 @@ int mdb_sample_merge_n(mdb_sample_cell *into, const mdb_sample_cell *from, uint6
 /* out[k] = cells[k].sum / cells[k].count, NaN where count == 0. Host memory, no context. */
 int mdb_sample_values(const mdb_sample_cell *cells, uint64_t n, double *out);
 
+/* Extension: the CHANGES between consecutive points per bucket of date_bin(width, ts, origin) and group - how much a
+ * counter grew and how often it restarted (increase() / rate() / resets(), non_negative_difference()), the largest
+ * step up and down of a window (ramp rates, spikes), how much a signal moved at all (total variation). In SQL
+ * v - lag(v) OVER (PARTITION BY series ORDER BY ts) followed by GROUP BY date_bin(...): GridExec -> WindowAggExec ->
+ * AggregateExec over every rebuilt point. Here every step inside a PMC-Mean segment is zero, so a (segment, bucket)
+ * pair is a count and a duration in O(1); a Swing segment's rows are arithmetic in registers; 64 bytes per cell leave
+ * the device.
+ *   request: mdb_change_request (mdb_format.h). buckets.t_lo / t_hi must be INT64_MIN / INT64_MAX and which_mask 0:
+ *     the buckets are the range. inout: row-major [n_groups][n_buckets] mdb_change_cell; a fresh cell is all-zero
+ *     bytes. A call MERGES into it.
+ *   Rows: those of mdb_grid_batch(in), in that order; no time range applies. Row r has ts(r), v(r) and
+ *     g(r) = group_of_segment[seg(r)] (NULL: 0).
+ *   Linked: exactly the rule of mdb_integral_buckets - rows r and r+1 are linked iff g(r+1) == g(r) and ts(r+1) > ts(r)
+ *     and ts(r+1) - ts(r) <= max_gap; inside segments, across segments, across the inputs of the list form; not across
+ *     calls. A segment that rebuilds to no row (end_time < start_time) links nothing across it.
+ *   The cell: a linked pair belongs to the bucket of its LATER row, (g, floor((ts(r+1) - origin) / width)), and is
+ *     never cut; if ts(r+1) lies outside [origin, origin + n_buckets*width) the pair is dropped, ts(r) may lie
+ *     anywhere. So the cells of adjacent buckets add up to the cell of their union, and the net change of a fully
+ *     linked stretch telescopes to its last value minus the value before its first row. Per pair, with
+ *     d = (double)v1 - (double)v0 (one rounding): count += 1 and duration += ts(r+1) - ts(r) (uint64_t, microseconds),
+ *     always; d > 0: rise += d, max_rise = max(max_rise, d); d < 0: n_fall += 1, fall += -d, reset_sum += (double)v1,
+ *     max_fall = max(max_fall, -d); d NaN (a NaN value, or inf - inf): rise += NaN and fall += NaN, the other members
+ *     as for d == 0, which touches only count and duration.
+ *   Finish: mdb_change_finish writes, per cell, MDB_CHANGE_NET rise - fall, MDB_CHANGE_VARIATION rise + fall,
+ *     MDB_CHANGE_INCREASE rise + reset_sum, MDB_CHANGE_RATE (rise + reset_sum) * 1e6 / duration (the increase per
+ *     second); NaN where count == 0, and for RATE also where duration == 0. mdb_change_merge_n adds the three integers
+ *     and the three sums and takes the larger of each maximum.
+ *   Exact promises: count, n_fall and duration are exact, always - also beside NaN and infinite values. max_rise and
+ *     max_fall are bit-exact: each is a maximum of individually rounded differences, which no order moves. A cell
+ *     whose rows all have one value has rise == fall == reset_sum == max_rise == max_fall == 0.0 exactly. A
+ *     non-decreasing stretch has n_fall == 0 and fall == 0.0 exactly.
+ *   Tolerance: for each of rise, fall and reset_sum, |got - exact| <= count * 2^-52 * S, S the sum of the magnitudes
+ *     of the member's terms in the cell: one rounding of 2^-53 per term, and at most (n-1) * 2^-53 * S for adding n
+ *     terms in any order through slices, tree and fold.
+ *   Determinism: two runs and the three forms agree bit for bit; no float atomics. MDB_AGG_BUCKET_SLICE_PAIRS and the
+ *     order of segments move the three sums by rounding only, the five other members not at all. Moving the origin by
+ *     a whole number of widths, with n_buckets moved along, gives the same bytes as long as the buckets added or
+ *     dropped hold no pair; where they do, the (segment, bucket) pairs in front of a cell's run change, the reduction
+ *     cuts the run elsewhere and the three sums move by rounding. Nothing overflows for any origin, width or
+ *     timestamp.
+ *   Errors (mdb_last_error set, inout untouched; what needs no device is checked before the device is used): a NULL
+ *     argument, width <= 0, n_groups == 0, an overflowing cell count, which_mask != 0, a time range in the bucket
+ *     request, reserved != 0, flags != 0, a negative max_gap, a group id >= n_groups on ANY row, the malformed-segment
+ *     classes of mdb_agg_buckets for the segments the request reaches and the neighbour whose first point it reads. An
+ *     empty batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_change_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                       const mdb_change_request *request, mdb_change_cell *inout);
+/* All device pointers: the batch, group_of_segment and inout are in HBM. */
+int mdb_change_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                           const mdb_change_request *request, mdb_change_cell *inout);
+/* Several host batches (rows in the order of the list) folded as one batch: a linked pair may cross from one input to
+ * the next. group_of_segment: one array per batch, or NULL. */
+int mdb_change_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                            uint32_t n_inputs, const mdb_change_request *request, mdb_change_cell *inout);
+/* into[k] merged with from[k] for k < n: integers and sums added, the larger of each maximum. Host memory, no context. */
+int mdb_change_merge_n(mdb_change_cell *into, const mdb_change_cell *from, uint64_t n);
+/* out[k] = the MDB_CHANGE_* `kind` of cells[k] (above); an unknown kind is an error. Host memory, no context. */
+int mdb_change_finish(const mdb_change_cell *cells, uint64_t n, uint32_t kind, double *out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -269,6 +269,33 @@ typedef struct mdb_sample_request {     /* 64 bytes, laid out like mdb_integral_
     uint32_t flags;              /* must be 0 */
 } mdb_sample_request;
 
+/* One cell of mdb_change_buckets*: the linked pairs of consecutive rows (mdb.h) whose LATER row lies in the bucket,
+ * with d = (double)v1 - (double)v0 per pair. count, n_fall and duration are exact; the three sums are f64 additions;
+ * the two maxima are bit-exact. A fresh cell is all-zero bytes; cells merge by adding the integers and the sums and
+ * taking the larger of each maximum (mdb_change_merge_n). */
+typedef struct mdb_change_cell {
+    uint64_t count;      /* the pairs */
+    uint64_t n_fall;     /* of which d < 0: the restarts of a counter */
+    uint64_t duration;   /* sum of ts(r+1) - ts(r), microseconds */
+    double   rise;       /* sum of d where d > 0 */
+    double   fall;       /* sum of -d where d < 0 */
+    double   reset_sum;  /* sum of (double)v1 where d < 0: what a restarted counter has counted since */
+    double   max_rise;   /* the largest d > 0, else 0 */
+    double   max_fall;   /* the largest -d where d < 0, else 0 */
+} mdb_change_cell;         /* 64 bytes */
+
+#define MDB_CHANGE_NET       0u  /* rise - fall */
+#define MDB_CHANGE_VARIATION 1u  /* rise + fall: the total variation */
+#define MDB_CHANGE_INCREASE  2u  /* rise + reset_sum: the increase of a counter that may restart */
+#define MDB_CHANGE_RATE      3u  /* the increase per second: (rise + reset_sum) * 1e6 / duration */
+
+typedef struct mdb_change_request {     /* 64 bytes, laid out like mdb_integral_request */
+    mdb_bucket_request buckets;  /* t_lo / t_hi must be INT64_MIN / INT64_MAX, which_mask 0: the buckets are the range */
+    int64_t  max_gap;            /* >= 0; INT64_MAX: no gap rule */
+    uint32_t reserved;           /* must be 0 */
+    uint32_t flags;              /* must be 0 */
+} mdb_change_request;
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -391,5 +418,19 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, instants) == 0);
 MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, max_gap) == 48);
 MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, method) == 56);
 MDB_LAYOUT_ASSERT(offsetof(mdb_sample_request, flags) == 60);
+MDB_LAYOUT_ASSERT(sizeof(mdb_change_cell) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, count) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, n_fall) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, duration) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, rise) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, fall) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, reset_sum) == 40);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, max_rise) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_cell, max_fall) == 56);
+MDB_LAYOUT_ASSERT(sizeof(mdb_change_request) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_request, buckets) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_request, max_gap) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_request, reserved) == 56);
+MDB_LAYOUT_ASSERT(offsetof(mdb_change_request, flags) == 60);
 
 #endif /* MDB_FORMAT_H */

@@ -265,6 +265,39 @@ class SampleRequestC(C.Structure):
 
 assert C.sizeof(SampleCellC) == 16 and C.sizeof(SampleRequestC) == 64
 
+MDB_CHANGE_NET = 0
+MDB_CHANGE_VARIATION = 1
+MDB_CHANGE_INCREASE = 2
+MDB_CHANGE_RATE = 3
+
+
+class ChangeCellC(C.Structure):
+    """mdb_change_cell: the linked pairs whose later row lies in a bucket (mdb_change_buckets*)."""
+    _fields_ = [
+        ("count", C.c_uint64),
+        ("n_fall", C.c_uint64),
+        ("duration", C.c_uint64),
+        ("rise", C.c_double),
+        ("fall", C.c_double),
+        ("reset_sum", C.c_double),
+        ("max_rise", C.c_double),
+        ("max_fall", C.c_double),
+    ]
+
+
+class ChangeRequestC(C.Structure):
+    """mdb_change_request: the buckets (no time range, which_mask 0) and the gap rule."""
+    _fields_ = [
+        ("buckets", BucketRequestC),
+        ("max_gap", C.c_int64),
+        ("reserved", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+assert C.sizeof(ChangeCellC) == 64 and C.sizeof(ChangeRequestC) == 64
+assert [getattr(ChangeCellC, name).offset for name, _ in ChangeCellC._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
+
 
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
@@ -431,6 +464,14 @@ _HIP_SYMBOLS = {
                                      C.POINTER(SampleRequestC), C.c_void_p]),
     "mdb_sample_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_sample_values": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mdb_change_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(ChangeRequestC),
+                                     C.c_void_p]),
+    "mdb_change_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(ChangeRequestC),
+                                         C.c_void_p]),
+    "mdb_change_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p),
+                                          C.c_uint32, C.POINTER(ChangeRequestC), C.c_void_p]),
+    "mdb_change_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_change_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,

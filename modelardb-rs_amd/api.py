@@ -347,6 +347,49 @@ def sample_values(cells):
     return out.reshape(cells.shape)
 
 
+# mdb_change_cell as a numpy record: the cells of mdb_change_buckets*, row-major [n_groups][n_buckets].
+CHANGE_CELL_DTYPE = np.dtype([("count", "<u8"), ("n_fall", "<u8"), ("duration", "<u8"), ("rise", "<f8"), ("fall", "<f8"),
+                              ("reset_sum", "<f8"), ("max_rise", "<f8"), ("max_fall", "<f8")])
+assert CHANGE_CELL_DTYPE.itemsize == C.sizeof(_abi.ChangeCellC) == 64
+MDB_CHANGE_NET = _abi.MDB_CHANGE_NET
+MDB_CHANGE_VARIATION = _abi.MDB_CHANGE_VARIATION
+MDB_CHANGE_INCREASE = _abi.MDB_CHANGE_INCREASE
+MDB_CHANGE_RATE = _abi.MDB_CHANGE_RATE
+
+
+def fresh_change_cells(shape):
+    """Fresh (empty) change cells: all-zero bytes."""
+    return np.zeros(shape, dtype=CHANGE_CELL_DTYPE)
+
+
+def change_merge(into, from_):
+    """into[k] merged with from_[k] in place (mdb_change_merge_n): the integers and the sums added, the larger of each
+    maximum. Two arrays of CHANGE_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != CHANGE_CELL_DTYPE or from_.dtype != CHANGE_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("change_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("change_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_change_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def change_finish(cells, kind):
+    """One figure per cell (mdb_change_finish): MDB_CHANGE_NET rise - fall, MDB_CHANGE_VARIATION rise + fall,
+    MDB_CHANGE_INCREASE rise + reset_sum, MDB_CHANGE_RATE the increase per second; NaN where count == 0 (RATE: or
+    duration == 0). Returns float64 of the shape of `cells`."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != CHANGE_CELL_DTYPE:
+        raise ValueError("change_finish takes an array of CHANGE_CELL_DTYPE")
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if lib.mdb_change_finish(flat.ctypes.data_as(C.c_void_p), flat.size, int(kind), out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -1427,6 +1470,84 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the batch spans more than one bucket can hold: use integral_buckets")
         return self.integral_buckets(batch, lo, hi - lo + 1, 1, groups, method, max_gap, None, n_groups).reshape(n_groups)
+
+    # ---- changes between consecutive points per bucket: increase, restarts, ramps, total variation ---------------
+
+    @staticmethod
+    def _change_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_change_cells((n_groups, n_buckets))
+        if cells.dtype != CHANGE_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of CHANGE_CELL_DTYPE")
+        return cells
+
+    @classmethod
+    def _change_request(cls, origin, width, n_buckets, n_groups, max_gap, reserved=0, flags=0):
+        request = _abi.ChangeRequestC()
+        request.buckets = cls._bucket_request(origin, width, n_buckets, n_groups, None, None, 0)
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.reserved = int(reserved)
+        request.flags = int(flags)
+        return request
+
+    def change_buckets(self, batch, origin, width, n_buckets, groups=None, max_gap=None, cells=None, n_groups=None):
+        """The changes between consecutive rows of one field per bucket [origin + b * width, origin + (b + 1) * width)
+        and group (mdb_change_buckets): cells of CHANGE_CELL_DTYPE. Two consecutive rows are linked when they share a
+        group, time moves forward and they are at most max_gap apart (None: no gap rule); a linked pair belongs to the
+        bucket of its later row. change_finish gives the net change, the total variation, the increase of a counter
+        and its rate. Returns `cells` (or fresh ones), shape (n_groups, n_buckets), merged in place. `groups` and
+        n_groups as for agg_buckets. Links do not cross calls: cut batches at series boundaries."""
+        return self.change_buckets_list([batch], origin, width, n_buckets, None if groups is None else [groups],
+                                        max_gap, cells, n_groups)
+
+    def change_buckets_list(self, batches, origin, width, n_buckets, groups=None, max_gap=None, cells=None,
+                            n_groups=None):
+        """Several host batches merged as one (mdb_change_buckets_list): a link may cross from one batch to the next;
+        `groups`: None or one array (or None) per batch."""
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._change_cells(cells, n_groups, n_buckets)
+        request = self._change_request(origin, width, n_buckets, n_groups, max_gap)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_change_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                     C.byref(request), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def change_buckets_dev(self, dev_segments, origin, width, n_buckets, groups=None, max_gap=None, cells=None,
+                           n_groups=None):
+        """mdb_change_buckets_dev on a resident batch: `groups` and `cells` are uploaded, the cells downloaded again."""
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._change_cells(cells, n_groups, n_buckets)
+        request = self._change_request(origin, width, n_buckets, n_groups, max_gap)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_change_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                        None if dev_groups is None else C.c_void_p(dev_groups),
+                                                        C.byref(request), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, CHANGE_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def change(self, batch, groups=None, n_groups=None, max_gap=None):
+        """The cells of `batch` as one bucket over its span, one per group (shape (n_groups,)): what a whole-batch
+        increase, restart count or total variation needs."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        if len(batch) == 0:
+            return fresh_change_cells(n_groups)
+        lo = int(min(np.min(batch.start_time), np.min(batch.end_time)))
+        hi = int(max(np.max(batch.start_time), np.max(batch.end_time)))
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the batch spans more than one bucket can hold: use change_buckets")
+        return self.change_buckets(batch, lo, hi - lo + 1, 1, groups, max_gap, None, n_groups).reshape(n_groups)
 
     # ---- sampling: the value of a series at regular instants (gap-fill, LOCF, interpolation) --------------------
 

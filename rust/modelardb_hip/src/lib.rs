@@ -37,10 +37,12 @@ pub use sys::{
     mdb_episode as Episode, mdb_episodes_request as EpisodesRequest, mdb_moments_cell as MomentsCell,
     mdb_integral_cell as IntegralCell, mdb_integral_request as IntegralRequest,
     mdb_sample_cell as SampleCell, mdb_sample_request as SampleRequest,
+    mdb_change_cell as ChangeCell, mdb_change_request as ChangeRequest,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
 pub use sys::{MDB_SAMPLE_EXACT, MDB_SAMPLE_LINEAR, MDB_SAMPLE_STEP};
+pub use sys::{MDB_CHANGE_INCREASE, MDB_CHANGE_NET, MDB_CHANGE_RATE, MDB_CHANGE_VARIATION};
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
@@ -411,6 +413,24 @@ pub fn sample_merge(into: &mut [SampleCell], from: &[SampleCell]) -> Result<()> 
 pub fn sample_values(cells: &[SampleCell]) -> Result<Vec<f64>> {
     let mut out = vec![0.0f64; cells.len()];
     check(unsafe { sys::mdb_sample_values(cells.as_ptr(), cells.len() as u64, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `into[k]` merged with `from[k]`: the integers and the sums added, the larger of each maximum - the merge of
+/// `mdb_change_buckets*` (host arithmetic, no GPU).
+pub fn change_merge(into: &mut [ChangeCell], from: &[ChangeCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_change_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// One figure per cell (host arithmetic, no GPU): `MDB_CHANGE_NET` `rise - fall`, `MDB_CHANGE_VARIATION`
+/// `rise + fall`, `MDB_CHANGE_INCREASE` `rise + reset_sum`, `MDB_CHANGE_RATE` the increase per second; NaN where
+/// `count == 0` (`MDB_CHANGE_RATE`: or `duration == 0`).
+pub fn change_finish(cells: &[ChangeCell], kind: u32) -> Result<Vec<f64>> {
+    let mut out = vec![0.0f64; cells.len()];
+    check(unsafe { sys::mdb_change_finish(cells.as_ptr(), cells.len() as u64, kind, out.as_mut_ptr()) })?;
     Ok(out)
 }
 
@@ -987,6 +1007,54 @@ impl Context {
         check(unsafe {
             sys::mdb_integral_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                            request, cells.as_mut_ptr())
+        })
+    }
+
+    /// Changes between consecutive rows: per bucket `[origin + b * width, origin + (b + 1) * width)` and group one
+    /// [`ChangeCell`] over the linked pairs whose later row lies in the bucket - how many, how many fell, the time
+    /// they span, the sums of the rises, of the falls and of the values after a fall, the largest rise and fall.
+    /// Rows are linked as for [`Context::integral_buckets`]; a pair is never cut. `cells` is row-major
+    /// `[n_groups][n_buckets]` (fresh: `ChangeCell::default()`); the batch is merged into it, so [`change_merge`] and
+    /// [`change_finish`] apply. `request.buckets` takes no time range and `which_mask` 0.
+    pub fn change_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &ChangeRequest,
+        cells: &mut [ChangeCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.buckets, cells.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_change_buckets(self.raw(), &segments.raw, groups, request, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::change_buckets`] for several batches at once (rows in the order of the slice), merged as one batch:
+    /// a linked pair may cross from one batch to the next. `group_of_segment`: `None`, or one entry per batch
+    /// (`None`: that batch's rows in group 0).
+    pub fn change_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &ChangeRequest,
+        cells: &mut [ChangeCell],
+    ) -> Result<()> {
+        check_bucket_cells(&request.buckets, cells.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_change_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                         request, cells.as_mut_ptr())
         })
     }
 

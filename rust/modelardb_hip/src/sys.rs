@@ -396,6 +396,69 @@ const _: () = assert!(std::mem::offset_of!(mdb_sample_request, max_gap) == 48);
 const _: () = assert!(std::mem::offset_of!(mdb_sample_request, method) == 56);
 const _: () = assert!(std::mem::offset_of!(mdb_sample_request, flags) == 60);
 
+/// One cell of `mdb_change_buckets*`: the linked pairs of consecutive rows whose LATER row lies in the bucket, with
+/// `d = v1 as f64 - v0 as f64` per pair. `count`, `n_fall` and `duration` are exact, the three sums f64 additions, the
+/// two maxima bit-exact. A fresh cell is all-zero bytes (`Default`); cells merge by adding the integers and the sums
+/// and taking the larger of each maximum.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_change_cell {
+    /// The pairs.
+    pub count: u64,
+    /// Of which `d < 0`: the restarts of a counter.
+    pub n_fall: u64,
+    /// Sum of `ts(r+1) - ts(r)`, microseconds.
+    pub duration: u64,
+    /// Sum of `d` where `d > 0`.
+    pub rise: f64,
+    /// Sum of `-d` where `d < 0`.
+    pub fall: f64,
+    /// Sum of `v1` where `d < 0`: what a restarted counter has counted since.
+    pub reset_sum: f64,
+    /// The largest `d > 0`, else 0.
+    pub max_rise: f64,
+    /// The largest `-d` where `d < 0`, else 0.
+    pub max_fall: f64,
+}
+
+/// `rise - fall`.
+pub const MDB_CHANGE_NET: u32 = 0;
+/// `rise + fall`: the total variation.
+pub const MDB_CHANGE_VARIATION: u32 = 1;
+/// `rise + reset_sum`: the increase of a counter that may restart.
+pub const MDB_CHANGE_INCREASE: u32 = 2;
+/// The increase per second: `(rise + reset_sum) * 1e6 / duration`.
+pub const MDB_CHANGE_RATE: u32 = 3;
+
+/// The request of `mdb_change_buckets*`. 64 bytes, laid out like `mdb_integral_request`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_change_request {
+    /// `t_lo` / `t_hi` must be `i64::MIN` / `i64::MAX` and `which_mask` 0: the buckets are the range.
+    pub buckets: mdb_bucket_request,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// Must be 0.
+    pub reserved: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_change_cell>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, count) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, n_fall) == 8);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, duration) == 16);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, rise) == 24);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, fall) == 32);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, reset_sum) == 40);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, max_rise) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_change_cell, max_fall) == 56);
+const _: () = assert!(std::mem::size_of::<mdb_change_request>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_change_request, buckets) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_change_request, max_gap) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_change_request, reserved) == 56);
+const _: () = assert!(std::mem::offset_of!(mdb_change_request, flags) == 60);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -605,6 +668,17 @@ unsafe extern "C" {
                               request: *const mdb_sample_request, inout: *mut mdb_sample_cell) -> c_int;
     pub fn mdb_sample_merge_n(into: *mut mdb_sample_cell, from: *const mdb_sample_cell, n: u64) -> c_int;
     pub fn mdb_sample_values(cells: *const mdb_sample_cell, n: u64, out: *mut f64) -> c_int;
+
+    // ---- changes between consecutive points per bucket: increase, restarts, ramps, variation (include/mdb.h) ----
+    pub fn mdb_change_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                              request: *const mdb_change_request, inout: *mut mdb_change_cell) -> c_int;
+    pub fn mdb_change_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                  request: *const mdb_change_request, inout: *mut mdb_change_cell) -> c_int;
+    pub fn mdb_change_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                   group_of_segment: *const *const u32, n_inputs: u32,
+                                   request: *const mdb_change_request, inout: *mut mdb_change_cell) -> c_int;
+    pub fn mdb_change_merge_n(into: *mut mdb_change_cell, from: *const mdb_change_cell, n: u64) -> c_int;
+    pub fn mdb_change_finish(cells: *const mdb_change_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
     // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
     pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                                   request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
