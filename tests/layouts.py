@@ -153,6 +153,19 @@ def three_parts(batch, mode, seed):
     return [relayout(batch.slice(cuts[k], cuts[k + 1]), modes[k], seed + 1 + k) for k in range(3)]
 
 
+def groups_of_parts(groups):
+    """One group id per row of a batch, cut as `cut` and `three_parts` cut the batch."""
+    cuts = part_cuts(len(groups))
+    return [groups[cuts[k]:cuts[k + 1]] for k in range(3)]
+
+
+def halves(batch):
+    """The batch in two parts, cut at a row that is none of part_cuts': what the second list of an operator on two
+    fields is handed, so that the two lists are cut at different rows."""
+    middle = len(batch) // 2 + 3
+    return [batch.slice(0, middle), batch.slice(middle, len(batch))]
+
+
 def out_of_line_offsets(column):
     """(buffer index, offset) of every out-of-line view, as two arrays."""
     words = column.views.view(np.int32).reshape(-1, 4)

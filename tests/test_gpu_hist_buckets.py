@@ -28,50 +28,9 @@ MAX_COUNTERS = 1 << 22
 COUNT = mdb.MDB_AGG_COUNT
 Q_LISTS = ([0.5], [0.0, 0.25, 0.5, 1.0], [0.999])
 
-_GRIDS = {}
-
-
-def _keys(values):
-    bits = np.asarray(values, dtype=np.float32).view(np.int32).astype(np.int64)
-    return bits ^ ((bits >> 31) & 0x7FFFFFFF)
-
-
-def _floats_of_keys(keys):
-    keys = np.asarray(keys, dtype=np.int64)
-    return (keys ^ ((keys >> 31) & 0x7FFFFFFF)).astype(np.int32).view(np.float32)
-
-
-def _f32(bits):
-    return np.array(bits, dtype=np.uint32).view(np.float32)
-
-
-def _grid(batch):
-    """(timestamps, values, keys, segment row of every point) of ora.grid_batch, computed once per batch."""
-    if id(batch) not in _GRIDS:
-        timestamps, values, rows, _ = ora.grid_batch(batch)
-        segment = np.repeat(np.arange(len(batch)), rows.astype(np.int64))
-        _GRIDS[id(batch)] = (batch, (timestamps.astype(np.int64), values, _keys(values), segment))
-    return _GRIDS[id(batch)][1]
-
-
-def _placed(batch, request, groups):
-    """(row = group * n_buckets + bucket, key) of every point the request holds."""
-    origin, width, n_buckets, t_lo, t_hi = request
-    timestamps, _, keys, segment = _grid(batch)
-    t_lo, t_hi = I64_MIN if t_lo is None else t_lo, I64_MAX if t_hi is None else t_hi
-    keep = (timestamps >= t_lo) & (timestamps <= t_hi) & (timestamps >= origin)
-    buckets = (timestamps[keep] - np.int64(origin)) // np.int64(width)
-    inside = buckets < n_buckets
-    group = np.zeros(int(keep.sum()), dtype=np.int64) if groups is None else groups.astype(np.int64)[segment[keep]]
-    return (group * n_buckets + buckets)[inside], keys[keep][inside]
-
-
-def _expected(batch, edges, request, groups=None, n_groups=1):
-    rows, keys = _placed(batch, request, groups)
-    n_buckets, n_cells = request[2], len(edges) + 1
-    cells = np.searchsorted(_keys(edges), keys, side="right")
-    counts = np.bincount(rows * n_cells + cells, minlength=n_groups * n_buckets * n_cells)
-    return counts.astype(np.uint64).reshape(n_groups, n_buckets, n_cells)
+from hist_buckets_cases import (GRIDS as _GRIDS, keys_of as _keys, floats_of_keys as _floats_of_keys, f32 as _f32,
+                                grid as _grid, placed as _placed, expected as _expected,
+                                expected_quantiles as _expected_quantiles)
 
 
 def _even_edges(keys, n_edges=4095):
@@ -383,25 +342,6 @@ def test_invariants_against_the_other_operators(hip):
 
 
 # ---- quantiles ------------------------------------------------------------------------------------------------------
-
-def _expected_quantiles(batch, request, q, groups=None, n_groups=1):
-    """(lo bits, hi bits, n_points, filled) per (group, bucket) from the sorted cells."""
-    rows, keys = _placed(batch, request, groups)
-    n_rows = n_groups * request[2]
-    order = np.lexsort((keys, rows))
-    rows, keys = rows[order], keys[order]
-    n_points = np.bincount(rows, minlength=n_rows).astype(np.uint64)
-    starts = np.concatenate([[0], np.cumsum(n_points.astype(np.int64))[:-1]])
-    lo, hi = np.zeros((n_rows, len(q)), dtype=np.uint32), np.zeros((n_rows, len(q)), dtype=np.uint32)
-    filled = n_points > 0
-    last = n_points[filled].astype(np.float64) - 1.0
-    for k, x in enumerate(q):
-        p = np.float64(x) * last
-        lo[filled, k] = _floats_of_keys(keys[starts[filled] + np.floor(p).astype(np.int64)]).view(np.uint32)
-        hi[filled, k] = _floats_of_keys(keys[starts[filled] + np.ceil(p).astype(np.int64)]).view(np.uint32)
-    shape = (n_groups, request[2])
-    return lo.reshape(shape + (len(q),)), hi.reshape(shape + (len(q),)), n_points.reshape(shape), filled.reshape(shape)
-
 
 def _check_quantiles(hip, batch, dev, request, q, groups, n_groups, what):
     origin, width, n_buckets, t_lo, t_hi = request

@@ -16,8 +16,15 @@ import ctypes
 import numpy as np
 import pytest
 
+import binned_cases as bc
+import comoments_cases as cc
+import episodes_cases as ec
+import integral_cases as ic
 import layouts
 import oracle_lib as ora
+import resident_orders as ro
+import sample_cases as sc
+import trend_cases as tc
 import modelardb_rs_amd as mdb
 from modelardb_rs_amd import MDB_AGG_COUNT, MDB_AGG_MAX, MDB_AGG_MIN, MDB_AGG_SUM
 
@@ -457,6 +464,230 @@ def test_histograms_and_quantiles(hip, world, default_decoder, mode):
                 assert n_points == n and lo.tobytes() == expected_lo and hi.tobytes() == expected_hi, (mode, t_lo, t_hi)
     finally:
         resident.free()
+
+
+# ---- the later operators: two fields, trends, episodes, integrals, samples ------------------------------------------
+# Requests: the two runs of buckets (or instants) of tests/resident_orders.py's corpus, in front of and behind the
+# corpus's gaps of 2^40. Per operator the canonical layout's host form is held to the operator's reference and its
+# test file's tolerance once; every form - on the canonical layout and on a relaid batch - then gives the bytes of
+# that one answer. The pair operators get x and y in DIFFERENT layouts, and lists cut at different rows: three parts of x
+# against two of y.
+
+class Later:
+    """What the later operators are asked about the corpus, and their references (computed once)."""
+
+    def __init__(self, world):
+        self.world = world
+        self.corpus = ro.corpus_a()
+        assert self.corpus.batch is world.batch                          # (layouts.corpus(), cached)
+        self.partner = self.corpus.partner.batch                         # the same series times 1.5: other segments
+        self.partner_groups = (np.arange(len(self.partner)) % 3).astype(np.uint32)
+        self.run_groups = ((np.arange(len(world.batch)) // ro.GROUP_RUN) % 3).astype(np.uint32)
+        self.edges = self.corpus.partner.edges
+        self.field, self.partner_field = cc.Field([world.batch]), cc.Field([self.partner])
+        self._relaid, self._parts, self._checked = {}, {}, {}
+
+    def partner_relaid(self, mode):
+        if mode not in self._relaid:
+            self._relaid[mode] = layouts.relayout(self.partner, mode, SEED + 11)
+        return self._relaid[mode]
+
+    def partner_parts(self, mode):
+        if mode not in self._parts:
+            self._parts[mode] = layouts.three_parts(self.partner_relaid(mode), mode, SEED + 11)
+        return self._parts[mode]
+
+    halves = staticmethod(layouts.halves)
+    groups_of_parts = staticmethod(layouts.groups_of_parts)
+
+    def canonical(self, key, run, check):
+        """run(...) on the canonical layout, once per key: its host form held to the reference by check(result), its
+        list and dev forms to the bytes of the host form (the contract: the three forms agree bit for bit)."""
+        if key not in self._checked:
+            result = run(None)
+            check(result)
+            _assert_forms(result, result, "canonical")
+            self._checked[key] = result
+        return self._checked[key]
+
+
+@pytest.fixture(scope="module")
+def later(world):
+    return Later(world)
+
+
+def _bytes_of(results):
+    return {name: [np.ascontiguousarray(item).tobytes() if isinstance(item, np.ndarray) else item for item in
+                   (result if isinstance(result, (list, tuple)) else [result])] for name, result in results.items()}
+
+
+def _assert_forms(got, canonical, mode):
+    """Every form of `got` ("host", "list", "dev", with the request's number behind) has the bytes of the canonical
+    layout's HOST form of the same request: the one answer that is tied to the reference."""
+    got, canonical = _bytes_of(got), _bytes_of(canonical)
+    assert got.keys() == canonical.keys() and len(got) % 3 == 0
+    for name in got:
+        anchored = "host" + name[len(name.split()[0]):]
+        assert name.split()[0] in ("host", "list", "dev") and anchored in canonical
+        assert got[name] == canonical[anchored], (mode, name, "differs from the canonical layout's host form")
+
+
+def _next_mode(mode):
+    return layouts.MODES[(layouts.MODES.index(mode) + 1) % len(layouts.MODES)]
+
+
+def _run_pair(hip, later, operator):
+    """comoments: x = the corpus, y = its partner; binned: x = the partner, y = the corpus. The host, list and dev forms
+    per span; mode None: both in the canonical layout."""
+    world = later.world
+    extra = () if operator == "comoments" else (later.edges,)
+    host, listed, dev = [getattr(hip, f"{operator}_buckets{form}") for form in ("", "_list", "_dev")]
+
+    def run(mode):
+        if operator == "comoments":
+            x = world.batch if mode is None else world.relaid(mode)
+            y = later.partner if mode is None else later.partner_relaid(_next_mode(mode))
+            xs = layouts.cut(x) if mode is None else world.parts(mode)
+            groups = world.groups
+        else:
+            x = later.partner if mode is None else later.partner_relaid(mode)
+            y = world.batch if mode is None else world.relaid(_next_mode(mode))
+            xs = layouts.cut(x) if mode is None else later.partner_parts(mode)
+            groups = later.partner_groups
+        ys = later.halves(y)
+        out = {}
+        dev_x, dev_y = hip.upload_segments(x), hip.upload_segments(y)
+        try:
+            for k, span in enumerate(later.corpus.spans):
+                out[f"host {k}"] = host(x, y, *extra, *span, groups=groups, n_groups=3)
+                out[f"list {k}"] = listed(xs, ys, *extra, *span, groups=later.groups_of_parts(groups), n_groups=3)
+                out[f"dev {k}"] = dev(dev_x, dev_y, *extra, *span, groups=groups, n_groups=3)
+        finally:
+            dev_x.free()
+            dev_y.free()
+        return out
+    return run
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_comoments(hip, world, later, default_decoder, mode):
+    run = _run_pair(hip, later, "comoments")
+
+    def check(canonical):
+        for k, span in enumerate(later.corpus.spans):
+            expected = cc.oracle(later.field, later.partner_field, world.groups, 3, *span)
+            assert int((expected["count"] > 0).sum()) > 100
+            cc.assert_cells(canonical[f"host {k}"], expected, f"comoments, span {k}")
+
+    _assert_forms(run(mode), later.canonical("comoments", run, check), mode)
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_binned(hip, world, later, default_decoder, mode):
+    run = _run_pair(hip, later, "binned")
+
+    def check(canonical):
+        for k, span in enumerate(later.corpus.spans):
+            expected = bc.oracle(later.partner_field, later.field, later.edges, later.partner_groups, 3, *span)
+            assert int((expected["count"] > 0).sum()) > 100
+            bc.assert_cells(canonical[f"host {k}"], expected, f"binned, span {k}")
+
+    _assert_forms(run(mode), later.canonical("binned", run, check), mode)
+
+
+def _run_single(hip, later, calls, spans, groups, **arguments):
+    """The host, list and dev forms of an operator on one batch, per span; mode None: the canonical layout."""
+    world = later.world
+    host, listed, dev = calls
+
+    def run(mode):
+        whole = world.batch if mode is None else world.relaid(mode)
+        parts = layouts.cut(whole) if mode is None else world.parts(mode)
+        out = {}
+        resident = hip.upload_segments(whole)
+        try:
+            for k, span in enumerate(spans):
+                out[f"host {k}"] = host(whole, *span, groups=groups, n_groups=3, **arguments)
+                out[f"list {k}"] = listed(parts, *span, groups=later.groups_of_parts(groups), n_groups=3, **arguments)
+                out[f"dev {k}"] = dev(resident, *span, groups=groups, n_groups=3, **arguments)
+        finally:
+            resident.free()
+        return out
+    return run
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_trend(hip, world, later, default_decoder, mode):
+    run = _run_single(hip, later, (hip.trend_buckets, hip.trend_buckets_list, hip.trend_buckets_dev), later.corpus.spans,
+                      world.groups)
+
+    def check(canonical):
+        special = 0
+        for k, span in enumerate(later.corpus.spans):
+            expected = tc.oracle(later.field, world.groups, 3, *span)
+            cc.assert_cells(canonical[f"host {k}"], expected, f"trend, span {k}")
+            special += tc.assert_x_side(canonical[f"host {k}"], expected, f"trend, span {k}")
+        assert special > 0
+
+    _assert_forms(run(mode), later.canonical("trend", run, check), mode)
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_integral(hip, world, later, default_decoder, mode):
+    arguments = dict(method=mdb.MDB_INTEGRAL_LINEAR, max_gap=ro.LINK_GAP)
+    run = _run_single(hip, later, (hip.integral_buckets, hip.integral_buckets_list, hip.integral_buckets_dev),
+                      later.corpus.spans, later.run_groups, **arguments)
+
+    def check(canonical):
+        special = 0
+        for k, span in enumerate(later.corpus.spans):
+            expected = ic.oracle(later.field, later.run_groups, 3, *span, ic.LINEAR, ro.LINK_GAP)
+            special += ic.assert_cells(canonical[f"host {k}"], expected, f"integral, span {k}")[1]
+        assert special > 0
+
+    _assert_forms(run(mode), later.canonical("integral", run, check), mode)
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_sample(hip, world, later, default_decoder, mode):
+    arguments = dict(method=mdb.MDB_SAMPLE_LINEAR, max_gap=ro.LINK_GAP)
+    run = _run_single(hip, later, (hip.sample_at, hip.sample_at_list, hip.sample_at_dev), later.corpus.sample_spans,
+                      later.run_groups, **arguments)
+
+    def check(canonical):
+        special = 0
+        for k, span in enumerate(later.corpus.sample_spans):
+            expected = sc.oracle(later.field, later.run_groups, 3, *span, sc.LINEAR, ro.LINK_GAP)
+            special += sc.assert_cells(canonical[f"host {k}"], expected, f"sample, span {k}")[1]
+        assert special > 0
+
+    _assert_forms(run(mode), later.canonical("sample", run, check), mode)
+
+
+@pytest.mark.parametrize("mode", layouts.MODES)
+def test_episodes(hip, world, later, default_decoder, mode):
+    band = world.filters()["band"]
+    arguments = dict(n_groups=3, max_gap=ro.EPISODE_GAP)
+
+    def run(mode):
+        whole = world.batch if mode is None else world.relaid(mode)
+        parts = layouts.cut(whole) if mode is None else world.parts(mode)
+        resident = hip.upload_segments(whole)
+        try:
+            return {"host": hip.episodes(whole, band, later.run_groups, **arguments),
+                    "list": hip.episodes_list(parts, band, later.groups_of_parts(later.run_groups), **arguments),
+                    "dev": hip.episodes_dev(resident, band, later.run_groups, **arguments)}
+        finally:
+            resident.free()
+
+    def check(canonical):
+        expected, magnitudes, n_rows, n_passing, _ = ec.reference(ec.Table(world.batch), band, groups=later.run_groups,
+                                                                  max_gap=ro.EPISODE_GAP)
+        episodes, rows, passing = canonical["host"]
+        assert (rows, passing) == (n_rows, n_passing) and len(expected) > 100
+        ec.assert_episodes(episodes, expected, magnitudes)
+
+    _assert_forms(run(mode), later.canonical("episodes", run, check), mode)
 
 
 # ---- upload and download ------------------------------------------------------------------------------------------

@@ -122,3 +122,30 @@ def test_three_parts_are_the_batch_in_other_layouts(canonical):
             indexes, offsets = layouts.out_of_line_offsets(part.values)
             late += sum(int(offsets[indexes == b].min()) >= 16 for b in np.unique(indexes))
         assert late >= 2, mode
+
+
+def test_the_lists_of_two_fields_are_cut_at_different_rows(canonical):
+    # What tests/test_gpu_layouts.py hands the operators on two fields: three parts of x (layouts.three_parts, their
+    # groups by layouts.groups_of_parts) against two parts of y (layouts.halves), x and y the corpus and its partner
+    # of tests/resident_orders.py in either role.
+    import resident_orders as ro
+    corpus = ro.corpus_a()
+    assert corpus.batch is canonical["batch"] or corpus.batch.identical(canonical["batch"])
+    fields = (corpus.batch, corpus.partner.batch)
+    assert len(fields[0]) != len(fields[1])
+    for x, y in (fields, fields[::-1]):
+        groups = (np.arange(len(x)) % 3).astype(np.uint32)
+        for mode in layouts.MODES[:2]:
+            parts = layouts.three_parts(layouts.relayout(x, mode, 11), mode, 11)
+            part_groups = layouts.groups_of_parts(groups)
+            assert [len(g) for g in part_groups] == [len(part) for part in parts] == [len(part) for part in layouts.cut(x)]
+            assert np.array_equal(np.concatenate(part_groups), groups)
+            assert mdb.SegmentBatch.concat(parts).identical(x)
+        two = layouts.halves(y)
+        assert len(two) == 2 and all(len(part) > 0 for part in two) and mdb.SegmentBatch.concat(two).identical(y)
+        # y's cut is at none of x's part_cuts, neither by row number nor in time: the row behind it begins inside a
+        # part of x, away from that part's first row
+        assert len(two[0]) not in layouts.part_cuts(len(x)) and len(two[0]) not in layouts.part_cuts(len(y))
+        cut_time = int(two[1].start_time[0])
+        x_cut_times = [int(x.start_time[row]) for row in layouts.part_cuts(len(x))[1:-1]]
+        assert cut_time not in x_cut_times and int(x.start_time[0]) < cut_time < int(x.start_time[-1])

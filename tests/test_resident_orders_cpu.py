@@ -7,6 +7,7 @@ import itertools
 import numpy as np
 import pytest
 
+import oracle_lib as ora
 import resident_orders as ro
 import modelardb_rs_amd as mdb
 from modelardb_rs_amd import _abi
@@ -31,6 +32,22 @@ def test_the_operator_table():
     for needed in ("grid", "grid range", "count", "min max", "all four", "range cut", "range whole", "buckets", "filter",
                    "grid filter", "mask", "buckets filter", "hist", "quantile", "download"):
         assert needed in names
+    # one entry per later resident entry point, sample_at_dev under two methods
+    later = [name for name, _, _ in ro.LATER]
+    assert later == ["m4", "moments", "hist buckets", "quantile buckets", "comoments", "binned", "trend", "integral",
+                     "sample", "sample step", "change", "episodes"]
+    assert names[-len(later):] == later and ro.K == 28
+    assert set(ro.CALLS) == set(ro.MEMBERS) == set(later)
+
+
+def test_the_rows_the_tests_name_are_distinct():
+    # (tests/test_gpu_resident_state.py: the freed-batch test's rows, the malformed-stream test's, the threads')
+    rows = ro.williams(ro.K)
+    for numbers in ([1, 6, 11, 14, 4, 9], [0, ro.K // 4, ro.K // 2, (3 * ro.K) // 4],
+                    *[[(upload + quarter * ro.K // 4) % ro.K for quarter in range(4)] for upload in range(3)]):
+        assert len({tuple(rows[number]) for number in numbers}) == len(numbers) and max(numbers) < ro.K
+    for schedule in range(ro.N_SCHEDULES):
+        assert schedule != (schedule + ro.K // 2) % ro.K
 
 
 @pytest.mark.parametrize("which", ["corpus_a", "corpus_b"])
@@ -39,6 +56,52 @@ def test_the_corpora_hold_what_the_tier_needs(which):
     ro.corpus_conditions(corpus)
     if which == "corpus_a":
         assert len(corpus.batch) == 468 and len(corpus.timestamps) == 110_679
+        assert corpus.partner is ro.corpus_b() and ro.corpus_b().partner is corpus
+
+
+def test_the_spans_lie_in_front_of_and_behind_the_gaps():
+    corpus = ro.corpus_a()
+    (front, width, n_front), (rear, _, n_rear) = corpus.spans
+    gaps = np.flatnonzero(np.diff(corpus.timestamps) > 1 << 31)
+    assert len(gaps) == 3
+    assert front < corpus.timestamps[0] and corpus.timestamps[gaps[0]] < front + width * n_front < corpus.timestamps[gaps[0] + 1]
+    # (the point behind the last gap ends a segment that begins in front of it: the rear span begins with the next)
+    assert corpus.timestamps[gaps[-1] + 1] < rear < corpus.timestamps[gaps[-1] + 2]
+    assert corpus.cut_range[1] < rear + width * n_rear <= corpus.cut_range[1] + width
+    # what the conditions are for: each of them fails on a request that misses what it asks for
+    only_front = ro.Corpus("front", corpus.batch, corpus.timestamps, corpus.values, partner=corpus.partner)
+    only_front.spans = (corpus.spans[0], (rear, width, 64))
+    with pytest.raises(AssertionError):
+        ro.span_conditions(only_front)          # (no long stream under the buckets)
+    ungrouped = ro.Corpus("neighbours apart", corpus.batch, corpus.timestamps, corpus.values, partner=corpus.partner)
+    ungrouped.run_groups = corpus.groups
+    with pytest.raises(AssertionError):
+        ro.span_conditions(ungrouped)           # (no link between two segments)
+    one_group = ro.Corpus("one group", corpus.batch, corpus.timestamps, corpus.values, partner=corpus.partner)
+    one_group.run_groups = np.zeros(len(corpus.batch), dtype=np.uint32)
+    with pytest.raises(AssertionError):
+        ro.episode_conditions(one_group)        # (no passing row in the second group)
+    with pytest.raises(AssertionError):
+        ro.span_conditions(ro.corpus_plain())   # (no NaN, no infinity)
+    ro.span_conditions(ro.corpus_plain(), non_finite=False)
+
+
+def test_the_split_digest_compares_the_exact_members_apart():
+    cells = mdb.fresh_moments_cells((2, 3))
+    cells["count"] = np.arange(6).reshape(2, 3)
+    cells["mean"] = 1.5
+    whole = ro.split_digest(*ro.MEMBERS["moments"](cells))
+    other = cells.copy()
+    other["m2"][1, 2] = np.nextafter(0.0, 1.0)
+    moved = ro.split_digest(*ro.MEMBERS["moments"](other))
+    assert moved != whole and ro.exact_part(moved) == ro.exact_part(whole)
+    other["count"][0, 0] += 1
+    assert ro.exact_part(ro.split_digest(*ro.MEMBERS["moments"](other))) != ro.exact_part(whole)
+    with pytest.raises(AssertionError):
+        ro.MEMBERS["moments"](mdb.fresh_m4_cells((2, 3)))   # (every member is named, or the split fails)
+    episodes = np.zeros(3, dtype=mdb.EPISODE_DTYPE)
+    exact, rounded = ro.MEMBERS["episodes"]((episodes, 7, 3))
+    assert ro.split_digest(exact, rounded) != ro.split_digest(*ro.MEMBERS["episodes"]((episodes, 7, 4)))
 
 
 def test_the_plain_corpus_shows_every_kept_sum_in_its_total():
@@ -68,6 +131,18 @@ def test_the_malformed_batch_is_the_corpus_and_one_row():
     same = [row for row in corpus.batch.rows() if row[3] == last[3] and row[6][: len(last[6])] == last[6]]
     assert last[0] == mdb.MDB_MACAQUE_V_ID and same and len(last[6]) == len(same[0][6]) // 2 > 12
     assert last[1] > corpus.batch.end_time[-1]
+    # ... and its partner: corpus_b and the same row with its payload whole, so the pair lines up and has one fault
+    broken = ro.malformed_corpus(corpus)
+    assert broken.batch.identical(batch) and broken.spans == corpus.spans and broken.cut_range == corpus.cut_range
+    other = broken.partner.batch
+    assert len(other) == len(corpus.partner.batch) + 1 and other.slice(0, len(other) - 1).identical(corpus.partner.batch)
+    whole = other.rows()[-1]
+    assert whole[:6] == last[:6] and whole[7:] == last[7:] and whole[6] == same[0][6]
+    timestamps = np.asarray(ora.grid_batch(other)[0])      # (whole: the oracle decodes it)
+    assert 200 <= len(timestamps) - len(corpus.timestamps) <= 400
+    assert timestamps[len(corpus.timestamps)] == last[1] and timestamps[-1] == last[2]
+    # every request but the episodes' ends in front of the row
+    assert max(corpus.cut_range[1], *[origin + width * n for origin, width, n in corpus.spans + corpus.sample_spans]) < corpus.batch.end_time[-1] < last[1]
 
 
 def _flipped(array, bit):
