@@ -992,6 +992,61 @@ int mdb_change_merge_n(mdb_change_cell *into, const mdb_change_cell *from, uint6
 /* out[k] = the MDB_CHANGE_* `kind` of cells[k] (above); an unknown kind is an error. Host memory, no context. */
 int mdb_change_finish(const mdb_change_cell *cells, uint64_t n, uint32_t kind, double *out);
 
+/* Extension: the TIME SPENT per value cell, per bucket of date_bin(width, ts, origin) and group - time in state, a
+ * load-duration curve, "the share of the day the rotor ran between 12 and 14 rpm", time above a limit per shift.
+ * Elsewhere state_agg / duration_in, a time-weighted histogram, or lag() over every rebuilt point followed by GROUP BY
+ * date_bin, width_bucket (GridExec -> WindowAggExec -> AggregateExec). mdb_hist_buckets counts points per value cell
+ * and mdb_integral_buckets integrates over time; this is the product of the two. A PMC-Mean segment on regular
+ * timestamps gives its share of a bucket in O(1), a Swing segment by the binary searches of mdb_hist_buckets.
+ *   request: mdb_dwell_request (mdb_format.h). buckets.t_lo / t_hi must be INT64_MIN / INT64_MAX and which_mask 0:
+ *     the buckets are the range. method must be MDB_DWELL_STEP, flags 0.
+ *   edges, cells: those of mdb_hist_buckets - 1 .. MDB_HIST_MAX_EDGES edges, strictly increasing in totalOrder; the
+ *     cell of a value is mdb_hist_cell_of; n_cells = n_edges + 1.
+ *   dwell: row-major uint64_t [n_groups][n_buckets][n_cells], microseconds. A call ADDS to it.
+ *   Rows and Linked: exactly those of mdb_integral_buckets - rows r and r+1 of mdb_grid_batch(in) are linked iff
+ *     g(r+1) == g(r) and ts(r+1) > ts(r) and ts(r+1) - ts(r) <= max_gap; inside segments, across segments, across the
+ *     inputs of the list form; not across calls. A segment that rebuilds to no row links nothing across it.
+ *   The cell: on a linked interval (t0, v0) - (t1, v1) the series holds v0 on [t0, t1). For every bucket b, with
+ *     a = max(t0, bucket start) and e = min(t1, bucket end): if e > a, dwell[g][b][cell_of(v0)] += e - a. An interval
+ *     may cross any number of bucket edges; bucket ends saturate at INT64_MAX. v1 is never read; the last row of a
+ *     linked run holds nothing. A non-finite v0 is placed by its totalOrder key like any other value: +NaN in the last
+ *     cell, -NaN in the first, -0.0 below an edge at +0.0.
+ *   Only STEP: under linear interpolation the instant at which a line crosses an edge is not an integer number of
+ *     microseconds, and nothing below would be exact. MDB_INTEGRAL_LINEAR's number (0) is refused by name, not
+ *     approximated.
+ *   Exact promises: everything is integer microseconds, so every number is exact. The cells of a (group, bucket) row
+ *     sum to mdb_integral_buckets' duration under MDB_INTEGRAL_STEP for the same request. Merging adjacent cells
+ *     gives the cells of the coarser edge list; adjacent buckets add up to the bucket of their union.
+ *   Determinism: integer atomics only; two runs and the three forms agree byte for byte, whatever the order of
+ *     segments or the cut of batches at series boundaries. Moving the origin by whole widths, with n_buckets moved
+ *     along, gives the same numbers.
+ *   Finish: mdb_dwell_share writes dwell / (sum over the row's cells) as f64, NaN where the sum is 0;
+ *     mdb_dwell_merge_n adds two arrays.
+ *   Errors (mdb_last_error set, dwell untouched; what needs no device is checked before the device is used): a NULL
+ *     argument, a bad edge list, width <= 0, n_groups == 0, an overflowing or non-fitting counter array, a time range
+ *     in the request, which_mask != 0, an unknown method, flags != 0, a negative max_gap, a group id >= n_groups on ANY
+ *     row, the malformed-segment classes of mdb_agg_buckets for the segments the request reaches. Of a segment's right
+ *     neighbour only start_time, the group and whether it rebuilds to a row are read, the last from its views and times
+ *     alone: a malformed neighbour that no bucket reaches is NOT reported (mdb_integral_buckets reads its first point
+ *     and fails on it) and counts as a segment with rows, unless its timestamps' length is negative. On such a batch
+ *     the promise about mdb_integral_buckets' duration is void: that call fails. An empty batch or n_buckets == 0
+ *     succeeds and changes nothing. */
+int mdb_dwell_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                      const mdb_dwell_request *request, const float *edges, uint32_t n_edges, uint64_t *dwell);
+/* All device pointers but request and edges: the batch, group_of_segment and dwell are in HBM. */
+int mdb_dwell_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                          const mdb_dwell_request *request, const float *edges, uint32_t n_edges, uint64_t *dwell);
+/* Several host batches (rows in the order of the list) folded as one batch: a linked interval may cross from one input
+ * to the next. group_of_segment: one array per batch, or NULL. */
+int mdb_dwell_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                           uint32_t n_inputs, const mdb_dwell_request *request, const float *edges, uint32_t n_edges,
+                           uint64_t *dwell);
+/* into[k] += from[k] for k < n. Host memory, no context. */
+int mdb_dwell_merge_n(uint64_t *into, const uint64_t *from, uint64_t n);
+/* out[row * n_cells + c] = dwell[row * n_cells + c] / (the sum of the row's n_cells cells) for row < n_rows, NaN where
+ * that sum is 0. Host memory, no context. */
+int mdb_dwell_share(const uint64_t *dwell, uint64_t n_rows, uint32_t n_cells, double *out);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

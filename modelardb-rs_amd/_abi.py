@@ -298,6 +298,21 @@ class ChangeRequestC(C.Structure):
 assert C.sizeof(ChangeCellC) == 64 and C.sizeof(ChangeRequestC) == 64
 assert [getattr(ChangeCellC, name).offset for name, _ in ChangeCellC._fields_] == [0, 8, 16, 24, 32, 40, 48, 56]
 
+MDB_DWELL_STEP = 1
+
+
+class DwellRequestC(C.Structure):
+    """mdb_dwell_request: the buckets (no time range, which_mask 0), the gap rule and the method (MDB_DWELL_STEP)."""
+    _fields_ = [
+        ("buckets", BucketRequestC),
+        ("max_gap", C.c_int64),
+        ("method", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+assert C.sizeof(DwellRequestC) == 64
+
 
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
@@ -472,6 +487,14 @@ _HIP_SYMBOLS = {
                                           C.c_uint32, C.POINTER(ChangeRequestC), C.c_void_p]),
     "mdb_change_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_change_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_dwell_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(DwellRequestC), C.c_void_p,
+                                    C.c_uint32, C.c_void_p]),
+    "mdb_dwell_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(DwellRequestC),
+                                        C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_dwell_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                         C.POINTER(DwellRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_dwell_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_dwell_share": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,

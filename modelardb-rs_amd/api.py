@@ -498,6 +498,37 @@ def are_compressed_timestamps_regular(data):
     return bool(regular.value)
 
 
+MDB_DWELL_STEP = _abi.MDB_DWELL_STEP
+
+
+def dwell_merge(into, from_):
+    """into[k] += from_[k] in place (mdb_dwell_merge_n): two uint64 arrays of dwell_buckets of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != np.uint64 or from_.dtype != np.uint64 or into.size != from_.size:
+        raise ValueError("dwell_merge takes two uint64 arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("dwell_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_dwell_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def dwell_share(dwell):
+    """The share of its (group, bucket) row's linked time each cell holds (mdb_dwell_share): dwell / the sum over the
+    last axis, NaN where that sum is 0. Returns float64 of the shape of `dwell`."""
+    lib = _abi.load_hip_library()
+    if dwell.dtype != np.uint64 or dwell.ndim < 1:
+        raise ValueError("dwell_share takes a uint64 array whose last axis is the cells")
+    n_cells = dwell.shape[-1]
+    flat = np.ascontiguousarray(dwell).reshape(-1)
+    out = np.empty(flat.size, dtype=np.float64)
+    if n_cells and lib.mdb_dwell_share(flat.ctypes.data_as(C.c_void_p), flat.size // n_cells, n_cells,
+                                       out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(dwell.shape)
+
+
 def _edges_array(edges):
     edges = np.ascontiguousarray(edges, dtype=np.float32)
     if edges.ndim != 1:
@@ -1548,6 +1579,80 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the batch spans more than one bucket can hold: use change_buckets")
         return self.change_buckets(batch, lo, hi - lo + 1, 1, groups, max_gap, None, n_groups).reshape(n_groups)
+
+    # ---- dwell: the time spent per value cell, per bucket ---------------------------------------------------------
+
+    @classmethod
+    def _dwell_request(cls, origin, width, n_buckets, n_groups, max_gap, method=MDB_DWELL_STEP, flags=0):
+        request = _abi.DwellRequestC()
+        request.buckets = cls._bucket_request(origin, width, n_buckets, n_groups, None, None, 0)
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.method = int(method)
+        request.flags = int(flags)
+        return request
+
+    def dwell_buckets(self, batch, edges, origin, width, n_buckets, groups=None, max_gap=None, dwell=None, n_groups=None):
+        """The microseconds one field spent in each value cell, ADDED to `dwell` (or to fresh zeros), shape (n_groups,
+        n_buckets, len(edges) + 1), per bucket [origin + b * width, origin + (b + 1) * width) and group
+        (mdb_dwell_buckets). Between two linked rows - same group, time moving forward, at most max_gap apart (None: no
+        gap rule) - the earlier value is held up to the later row; the cells are those of hist_buckets. dwell_share
+        gives the share of each row's linked time. `groups` and n_groups as for agg_buckets. Links do not cross calls:
+        cut batches at series boundaries."""
+        return self.dwell_buckets_list([batch], edges, origin, width, n_buckets, None if groups is None else [groups],
+                                       max_gap, dwell, n_groups)
+
+    def dwell_buckets_list(self, batches, edges, origin, width, n_buckets, groups=None, max_gap=None, dwell=None,
+                           n_groups=None):
+        """Several host batches as one (mdb_dwell_buckets_list): a link may cross from one batch to the next; `groups`:
+        None or one array (or None) per batch."""
+        edges = _edges_array(edges)
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, dwell, batch_groups)
+        dwell = self._hist_bucket_counts(dwell, n_groups, n_buckets, len(edges) + 1)
+        request = self._dwell_request(origin, width, n_buckets, n_groups, max_gap)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_dwell_buckets_list(self.handle, pointers, group_pointers, len(views), C.byref(request),
+                                                    edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                    dwell.ctypes.data_as(C.c_void_p)))
+        return dwell
+
+    def dwell_buckets_dev(self, dev_segments, edges, origin, width, n_buckets, groups=None, max_gap=None, dwell=None,
+                          n_groups=None):
+        """mdb_dwell_buckets_dev on a resident batch: `groups` and `dwell` are uploaded, the counters downloaded again."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, dwell, [groups])
+        dwell = self._hist_bucket_counts(dwell, n_groups, n_buckets, len(edges) + 1)
+        request = self._dwell_request(origin, width, n_buckets, n_groups, max_gap)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_dwell = self.upload_array(dwell)
+        try:
+            self._check(self.lib.mdb_dwell_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                       None if dev_groups is None else C.c_void_p(dev_groups),
+                                                       C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                       C.c_void_p(dev_dwell)))
+            dwell[...] = self.download_array(dev_dwell, dwell.size, np.uint64).reshape(dwell.shape)
+        finally:
+            self.dev_free(dev_dwell)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return dwell
+
+    def dwell(self, batch, edges, groups=None, n_groups=None, max_gap=None):
+        """The microseconds per value cell of `batch` as one bucket over its span, per group (shape (n_groups,
+        len(edges) + 1)): time in state of a whole batch."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        if len(batch) == 0:
+            return np.zeros((n_groups, len(_edges_array(edges)) + 1), dtype=np.uint64)
+        lo = int(min(np.min(batch.start_time), np.min(batch.end_time)))
+        hi = int(max(np.max(batch.start_time), np.max(batch.end_time)))
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the batch spans more than one bucket can hold: use dwell_buckets")
+        return self.dwell_buckets(batch, edges, lo, hi - lo + 1, 1, groups, max_gap, None, n_groups).reshape(n_groups, -1)
 
     # ---- sampling: the value of a series at regular instants (gap-fill, LOCF, interpolation) --------------------
 

@@ -38,11 +38,13 @@ pub use sys::{
     mdb_integral_cell as IntegralCell, mdb_integral_request as IntegralRequest,
     mdb_sample_cell as SampleCell, mdb_sample_request as SampleRequest,
     mdb_change_cell as ChangeCell, mdb_change_request as ChangeRequest,
+    mdb_dwell_request as DwellRequest,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
 pub use sys::{MDB_SAMPLE_EXACT, MDB_SAMPLE_LINEAR, MDB_SAMPLE_STEP};
 pub use sys::{MDB_CHANGE_INCREASE, MDB_CHANGE_NET, MDB_CHANGE_RATE, MDB_CHANGE_VARIATION};
+pub use sys::MDB_DWELL_STEP;
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
@@ -431,6 +433,25 @@ pub fn change_merge(into: &mut [ChangeCell], from: &[ChangeCell]) -> Result<()> 
 pub fn change_finish(cells: &[ChangeCell], kind: u32) -> Result<Vec<f64>> {
     let mut out = vec![0.0f64; cells.len()];
     check(unsafe { sys::mdb_change_finish(cells.as_ptr(), cells.len() as u64, kind, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `into[k] += from[k]`: the merge of two counter arrays of `mdb_dwell_buckets*` (host arithmetic, no GPU).
+pub fn dwell_merge(into: &mut [u64], from: &[u64]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} counters merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_dwell_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The share of its (group, bucket) row's linked time each cell holds: `dwell / sum over the row's n_cells cells`, NaN
+/// where that sum is 0 (host arithmetic, no GPU). `dwell.len()` must be a multiple of `n_cells`.
+pub fn dwell_share(dwell: &[u64], n_cells: u32) -> Result<Vec<f64>> {
+    if n_cells == 0 || dwell.len() % n_cells as usize != 0 {
+        return Err(HipError(format!("{} counters are no whole number of rows of {} cells", dwell.len(), n_cells)));
+    }
+    let mut out = vec![0.0f64; dwell.len()];
+    check(unsafe { sys::mdb_dwell_share(dwell.as_ptr(), (dwell.len() / n_cells as usize) as u64, n_cells, out.as_mut_ptr()) })?;
     Ok(out)
 }
 
@@ -1311,6 +1332,59 @@ impl Context {
         check(unsafe {
             sys::mdb_hist_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                        request, edges.as_ptr(), n_edges, counts.as_mut_ptr())
+        })
+    }
+
+    /// The microseconds one field spent in each value cell, per bucket of `date_bin(width, ts, origin)` and group:
+    /// `dwell` is row-major `[n_groups][n_buckets][edges.len() + 1]` and the batch is ADDED to it. Between two linked
+    /// rows (the rule of [`Context::integral_buckets`]) the earlier value is held up to the later row; the cells are
+    /// those of [`Context::hist_buckets`]. `request.method` must be [`MDB_DWELL_STEP`]; [`dwell_merge`] and
+    /// [`dwell_share`] apply.
+    pub fn dwell_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &DwellRequest,
+        edges: &[f32],
+        dwell: &mut [u64],
+    ) -> Result<()> {
+        check_hist_bucket_cells(&request.buckets, edges.len() as u64 + 1, dwell.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_dwell_buckets(self.raw(), &segments.raw, groups, request, edges.as_ptr(), n_edges, dwell.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::dwell_buckets`] for several batches at once (rows in the order of the slice), folded as one batch: a
+    /// link may cross from one batch to the next. `group_of_segment`: `None`, or one entry per batch (`None`: that
+    /// batch's rows in group 0).
+    pub fn dwell_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &DwellRequest,
+        edges: &[f32],
+        dwell: &mut [u64],
+    ) -> Result<()> {
+        check_hist_bucket_cells(&request.buckets, edges.len() as u64 + 1, dwell.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_dwell_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                        request, edges.as_ptr(), n_edges, dwell.as_mut_ptr())
         })
     }
 

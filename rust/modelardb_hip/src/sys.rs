@@ -459,6 +459,30 @@ const _: () = assert!(std::mem::offset_of!(mdb_change_request, max_gap) == 48);
 const _: () = assert!(std::mem::offset_of!(mdb_change_request, reserved) == 56);
 const _: () = assert!(std::mem::offset_of!(mdb_change_request, flags) == 60);
 
+/// The only method of `mdb_dwell_buckets*`: the earlier value of a linked interval is held up to the later row
+/// (`MDB_INTEGRAL_STEP`'s number; 0, linear interpolation, is refused).
+pub const MDB_DWELL_STEP: u32 = 1;
+
+/// The request of `mdb_dwell_buckets*`. 64 bytes, laid out like `mdb_integral_request`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_dwell_request {
+    /// `t_lo` / `t_hi` must be `i64::MIN` / `i64::MAX` and `which_mask` 0: the buckets are the range.
+    pub buckets: mdb_bucket_request,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// `MDB_DWELL_STEP`.
+    pub method: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_dwell_request>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, buckets) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, max_gap) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, method) == 56);
+const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, flags) == 60);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -679,6 +703,20 @@ unsafe extern "C" {
                                    request: *const mdb_change_request, inout: *mut mdb_change_cell) -> c_int;
     pub fn mdb_change_merge_n(into: *mut mdb_change_cell, from: *const mdb_change_cell, n: u64) -> c_int;
     pub fn mdb_change_finish(cells: *const mdb_change_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
+
+    // ---- the time spent per value cell, per bucket: time in state, load-duration curves (include/mdb.h) ----
+    pub fn mdb_dwell_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                             request: *const mdb_dwell_request, edges: *const f32, n_edges: u32,
+                             dwell: *mut u64) -> c_int;
+    pub fn mdb_dwell_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                 request: *const mdb_dwell_request, edges: *const f32, n_edges: u32,
+                                 dwell: *mut u64) -> c_int;
+    pub fn mdb_dwell_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                  group_of_segment: *const *const u32, n_inputs: u32,
+                                  request: *const mdb_dwell_request, edges: *const f32, n_edges: u32,
+                                  dwell: *mut u64) -> c_int;
+    pub fn mdb_dwell_merge_n(into: *mut u64, from: *const u64, n: u64) -> c_int;
+    pub fn mdb_dwell_share(dwell: *const u64, n_rows: u64, n_cells: u32, out: *mut f64) -> c_int;
     // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
     pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                                   request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
