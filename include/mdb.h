@@ -1047,6 +1047,60 @@ int mdb_dwell_merge_n(uint64_t *into, const uint64_t *from, uint64_t n);
  * that sum is 0. Host memory, no context. */
 int mdb_dwell_share(const uint64_t *dwell, uint64_t n_rows, uint32_t n_cells, double *out);
 
+/* Extension: the TRANSITIONS between value cells, per bucket of date_bin(width, ts, origin) and group - how often the
+ * series went from one band to another: starts per day of a machine (stopped -> running), upward crossings of a limit
+ * per shift, the state-transition matrix of an operating mode. Elsewhere the transitions half of state_agg, a
+ * level-crossing count, or lag() over every rebuilt point followed by GROUP BY date_bin, width_bucket(lag_v),
+ * width_bucket(v) (GridExec -> WindowAggExec -> AggregateExec). mdb_dwell_buckets is the time half of that question,
+ * mdb_change_buckets counts falls of any size and not crossings of a level. Inside a PMC-Mean segment every pair stays
+ * in its cell, O(1) per bucket; along a Swing line the cells change monotonically and the few pairs that change cell
+ * are found by the binary searches of mdb_hist_buckets.
+ *   request: mdb_transit_request (mdb_format.h). buckets.t_lo / t_hi must be INT64_MIN / INT64_MAX and which_mask 0:
+ *     the buckets are the range. reserved and flags must be 0, max_gap >= 0.
+ *   edges, cells: those of mdb_hist_buckets - 1 .. MDB_HIST_MAX_EDGES edges, strictly increasing in totalOrder; the
+ *     cell of a value is mdb_hist_cell_of; n_cells = n_edges + 1. A non-finite value is placed by its totalOrder key
+ *     as in mdb_dwell_buckets: +NaN in the last cell, -NaN in the first, -0.0 below an edge at +0.0.
+ *   counts: row-major uint64_t [n_groups][n_buckets][n_cells][n_cells], indexed [from][to]. A call ADDS to it.
+ *   Rows and Linked: exactly those of mdb_integral_buckets - inside segments, across segments, across the inputs of
+ *     the list form; not across calls. A segment that rebuilds to no row links nothing across it.
+ *   The counter: mdb_change_buckets' rule. A linked pair (t0, v0) - (t1, v1) belongs to the bucket b of its LATER row
+ *     and is never cut; it is dropped if t1 lies outside the buckets, t0 may lie anywhere. Each pair does
+ *     counts[g][b][cell_of(v0)][cell_of(v1)] += 1.
+ *   Finish: mdb_transit_crossings writes, per (group, bucket) row and edge e < n_edges, up[row][e] = the sum of
+ *     counts[from <= e < to] and down[row][e] = the sum of counts[to <= e < from]: the pairs that went over edge e
+ *     upwards and downwards. mdb_transit_merge_n adds two arrays.
+ *   Exact promises: everything is a count, so every number is exact. (a) The n_cells^2 counters of a (group, bucket)
+ *     row sum to mdb_change_buckets' count for the same request. (b) Adding the blocks of adjacent cells gives the
+ *     matrix under the coarser edge list. (c) Adjacent buckets add up to the bucket of their union; moving the origin
+ *     by whole widths, with n_buckets moved along, gives the same numbers. (d) The sum over `from` of
+ *     counts[..][from][to] is the number of rows of the bucket in cell `to` that have a linked predecessor: for one
+ *     fully linked series mdb_hist_buckets' count minus the first row. (e) Over buckets that cover one fully linked
+ *     run, the sum over the buckets of up[e] - down[e] is (cell(last) > e) - (cell(first) > e). (f) The sum of
+ *     counts[from > to] is at most mdb_change_buckets' n_fall.
+ *   Determinism: integer atomics only; two runs and the three forms agree byte for byte, whatever the order of
+ *     segments or the cut of batches at series boundaries.
+ *   Errors (mdb_last_error set, counts untouched; what needs no device is checked before the device is used): a NULL
+ *     argument, a bad edge list, width <= 0, n_groups == 0, n_groups * n_buckets * n_cells^2 overflowing or not
+ *     fitting the device, a time range in the request, which_mask, reserved or flags != 0, a negative max_gap, a
+ *     group id >= n_groups on ANY row, the malformed-segment classes of mdb_agg_buckets for the segments the request
+ *     reaches and for the right neighbour whose first point a segment the request reaches may read (as
+ *     mdb_change_buckets). An empty batch or n_buckets == 0 succeeds and changes nothing. */
+int mdb_transit_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                        const mdb_transit_request *request, const float *edges, uint32_t n_edges, uint64_t *counts);
+/* All device pointers but request and edges: the batch, group_of_segment and counts are in HBM. */
+int mdb_transit_buckets_dev(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,
+                            const mdb_transit_request *request, const float *edges, uint32_t n_edges, uint64_t *counts);
+/* Several host batches (rows in the order of the list) folded as one batch: a linked pair may cross from one input to
+ * the next. group_of_segment: one array per batch, or NULL. */
+int mdb_transit_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
+                             uint32_t n_inputs, const mdb_transit_request *request, const float *edges, uint32_t n_edges,
+                             uint64_t *counts);
+/* into[k] += from[k] for k < n. Host memory, no context. */
+int mdb_transit_merge_n(uint64_t *into, const uint64_t *from, uint64_t n);
+/* Per row < n_rows of n_cells * n_cells counters [from][to] and edge e < n_cells - 1: up[row * (n_cells - 1) + e] and
+ * down[...] as above. n_cells must be at least 1 (1: nothing is written). Host memory, no context. */
+int mdb_transit_crossings(const uint64_t *counts, uint64_t n_rows, uint32_t n_cells, uint64_t *up, uint64_t *down);
+
 /* ---- fit: replaces try_compress_univariate_time_series
  *      (crates/modelardb_compression/src/compression.rs:191-275), called per field column by
  *      crates/modelardb_server/src/storage/uncompressed_data_manager.rs:563-581 and, through

@@ -306,6 +306,14 @@ typedef struct mdb_dwell_request {      /* 64 bytes, laid out like mdb_integral_
     uint32_t flags;              /* must be 0 */
 } mdb_dwell_request;
 
+/* The request of mdb_transit_buckets*: transitions between value cells. Its output is uint64_t counters, no cell struct. */
+typedef struct mdb_transit_request {    /* 64 bytes, laid out like mdb_change_request */
+    mdb_bucket_request buckets;  /* t_lo / t_hi must be INT64_MIN / INT64_MAX, which_mask 0: the buckets are the range */
+    int64_t  max_gap;            /* >= 0; INT64_MAX: no gap rule */
+    uint32_t reserved;           /* must be 0 */
+    uint32_t flags;              /* must be 0 */
+} mdb_transit_request;
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -447,5 +455,10 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_dwell_request, buckets) == 0);
 MDB_LAYOUT_ASSERT(offsetof(mdb_dwell_request, max_gap) == 48);
 MDB_LAYOUT_ASSERT(offsetof(mdb_dwell_request, method) == 56);
 MDB_LAYOUT_ASSERT(offsetof(mdb_dwell_request, flags) == 60);
+MDB_LAYOUT_ASSERT(sizeof(mdb_transit_request) == 64);
+MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, buckets) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, max_gap) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, reserved) == 56);
+MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, flags) == 60);
 
 #endif /* MDB_FORMAT_H */

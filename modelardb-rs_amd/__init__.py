@@ -15,5 +15,5 @@ from ._abi import (  # noqa: F401
 from .segments import BinaryViewColumn, SegmentBatch, error_bound  # noqa: F401
 from .api import (  # noqa: F401
     AGG_STATE_DTYPE, CHANGE_CELL_DTYPE, COMOMENTS_CELL_DTYPE, EPISODE_DTYPE, INTEGRAL_CELL_DTYPE, SAMPLE_CELL_DTYPE, COMOMENTS_KINDS, M4_CELL_DTYPE, MOMENTS_CELL_DTYPE, Context, DeviceSegments, HipError, agg_merge_n, are_compressed_timestamps_regular,
-    change_finish, change_merge, dwell_merge, dwell_share, fresh_change_cells, comm_unique_id, comoments_finish, comoments_merge, comoments_moments, fresh_agg_states, fresh_comoments_cells, fresh_integral_cells, fresh_sample_cells, fresh_m4_cells, fresh_moments_cells, hist_cell_of, integral_average, integral_merge, sample_merge, sample_values, m4_merge, mask_words, moments_merge, moments_variance, quantile_positions, unpack_mask, is_value_within_error_bound, value_filter, value_filter_bits,
+    change_finish, change_merge, dwell_merge, dwell_share, transit_crossings, transit_merge, fresh_change_cells, comm_unique_id, comoments_finish, comoments_merge, comoments_moments, fresh_agg_states, fresh_comoments_cells, fresh_integral_cells, fresh_sample_cells, fresh_m4_cells, fresh_moments_cells, hist_cell_of, integral_average, integral_merge, sample_merge, sample_values, m4_merge, mask_words, moments_merge, moments_variance, quantile_positions, unpack_mask, is_value_within_error_bound, value_filter, value_filter_bits,
 )

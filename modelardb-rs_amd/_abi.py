@@ -314,6 +314,19 @@ class DwellRequestC(C.Structure):
 assert C.sizeof(DwellRequestC) == 64
 
 
+class TransitRequestC(C.Structure):
+    """mdb_transit_request: the buckets (no time range, which_mask 0) and the gap rule; reserved and flags are 0."""
+    _fields_ = [
+        ("buckets", BucketRequestC),
+        ("max_gap", C.c_int64),
+        ("reserved", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+assert C.sizeof(TransitRequestC) == 64
+
+
 class M4CellC(C.Structure):
     """mdb_m4_cell: the first, last, lowest and highest point of one bucket and group (mdb_m4_buckets*)."""
     _fields_ = [
@@ -495,6 +508,14 @@ _HIP_SYMBOLS = {
                                          C.POINTER(DwellRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
     "mdb_dwell_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_dwell_share": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_transit_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(TransitRequestC),
+                                      C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_transit_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(TransitRequestC),
+                                          C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_transit_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.POINTER(C.c_void_p), C.c_uint32,
+                                           C.POINTER(TransitRequestC), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "mdb_transit_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_transit_crossings": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mdb_episodes_count_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC),
                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mdb_episodes_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(EpisodesRequestC), C.c_void_p,

@@ -529,6 +529,38 @@ def dwell_share(dwell):
     return out.reshape(dwell.shape)
 
 
+def transit_merge(into, from_):
+    """into[k] += from_[k] in place (mdb_transit_merge_n): two uint64 arrays of transit_buckets of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != np.uint64 or from_.dtype != np.uint64 or into.size != from_.size:
+        raise ValueError("transit_merge takes two uint64 arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("transit_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_transit_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def transit_crossings(counts):
+    """The pairs that went over each edge (mdb_transit_crossings): `counts` is uint64 (..., n_cells, n_cells), indexed
+    [from][to]; returns (up, down), uint64 of shape (..., n_cells - 1): up[..., e] is the sum of counts[from <= e < to],
+    down[..., e] the sum of counts[to <= e < from]."""
+    lib = _abi.load_hip_library()
+    if counts.dtype != np.uint64 or counts.ndim < 2 or counts.shape[-1] != counts.shape[-2] or counts.shape[-1] < 1:
+        raise ValueError("transit_crossings takes a uint64 array whose last two axes are the cells [from][to]")
+    n_cells = counts.shape[-1]
+    flat = np.ascontiguousarray(counts).reshape(-1)
+    n_rows = flat.size // (n_cells * n_cells)
+    up = np.zeros(n_rows * (n_cells - 1), dtype=np.uint64)
+    down = np.zeros(n_rows * (n_cells - 1), dtype=np.uint64)
+    if lib.mdb_transit_crossings(flat.ctypes.data_as(C.c_void_p), n_rows, n_cells, up.ctypes.data_as(C.c_void_p),
+                                 down.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    shape = counts.shape[:-2] + (n_cells - 1,)
+    return up.reshape(shape), down.reshape(shape)
+
+
 def _edges_array(edges):
     edges = np.ascontiguousarray(edges, dtype=np.float32)
     if edges.ndim != 1:
@@ -1653,6 +1685,93 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the batch spans more than one bucket can hold: use dwell_buckets")
         return self.dwell_buckets(batch, edges, lo, hi - lo + 1, 1, groups, max_gap, None, n_groups).reshape(n_groups, -1)
+
+    # ---- transit: transitions between value cells, per bucket ------------------------------------------------------
+
+    @classmethod
+    def _transit_request(cls, origin, width, n_buckets, n_groups, max_gap, reserved=0, flags=0):
+        request = _abi.TransitRequestC()
+        request.buckets = cls._bucket_request(origin, width, n_buckets, n_groups, None, None, 0)
+        request.max_gap = INT64_MAX if max_gap is None else int(max_gap)
+        request.reserved = int(reserved)
+        request.flags = int(flags)
+        return request
+
+    @staticmethod
+    def _transit_counts(counts, n_groups, n_buckets, n_cells):
+        if counts is None:
+            return np.zeros((n_groups, n_buckets, n_cells, n_cells), dtype=np.uint64)
+        shape = (n_groups, n_buckets, n_cells, n_cells)
+        if counts.dtype != np.uint64 or counts.shape != shape or not counts.flags.c_contiguous:
+            raise ValueError(f"counts must be a contiguous {shape} array of uint64")
+        return counts
+
+    def transit_buckets(self, batch, edges, origin, width, n_buckets, groups=None, max_gap=None, counts=None,
+                        n_groups=None):
+        """The linked pairs of rows of one field by the value cells they go from and to, ADDED to `counts` (or to fresh
+        zeros), shape (n_groups, n_buckets, len(edges) + 1, len(edges) + 1) indexed [from][to], per bucket [origin + b *
+        width, origin + (b + 1) * width) and group (mdb_transit_buckets). Two rows are linked when they share a group,
+        time moves forward and they are at most max_gap apart (None: no gap rule); a pair belongs to the bucket of its
+        later row; the cells are those of hist_buckets. transit_crossings gives the crossings of each edge. `groups`
+        and n_groups as for agg_buckets. Links do not cross calls: cut batches at series boundaries."""
+        return self.transit_buckets_list([batch], edges, origin, width, n_buckets, None if groups is None else [groups],
+                                         max_gap, counts, n_groups)
+
+    def transit_buckets_list(self, batches, edges, origin, width, n_buckets, groups=None, max_gap=None, counts=None,
+                             n_groups=None):
+        """Several host batches as one (mdb_transit_buckets_list): a pair may cross from one batch to the next;
+        `groups`: None or one array (or None) per batch."""
+        edges = _edges_array(edges)
+        batch_groups = [None] * len(batches) if groups is None else [self._groups_array(g, len(b))
+                                                                     for g, b in zip(groups, batches)]
+        n_groups = self._n_groups(n_groups, counts, batch_groups)
+        counts = self._transit_counts(counts, n_groups, n_buckets, len(edges) + 1)
+        request = self._transit_request(origin, width, n_buckets, n_groups, max_gap)
+        views = [batch.as_c() for batch in batches]
+        pointers = (C.POINTER(_abi.SegmentsC) * max(len(views), 1))(*[C.pointer(view) for view in views])
+        group_pointers = (C.c_void_p * max(len(views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_transit_buckets_list(self.handle, pointers, group_pointers, len(views),
+                                                      C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                      counts.ctypes.data_as(C.c_void_p)))
+        return counts
+
+    def transit_buckets_dev(self, dev_segments, edges, origin, width, n_buckets, groups=None, max_gap=None, counts=None,
+                            n_groups=None):
+        """mdb_transit_buckets_dev on a resident batch: `groups` and `counts` are uploaded, the counters downloaded
+        again."""
+        edges = _edges_array(edges)
+        groups = self._groups_array(groups, len(dev_segments))
+        n_groups = self._n_groups(n_groups, counts, [groups])
+        counts = self._transit_counts(counts, n_groups, n_buckets, len(edges) + 1)
+        request = self._transit_request(origin, width, n_buckets, n_groups, max_gap)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_counts = self.upload_array(counts)
+        try:
+            self._check(self.lib.mdb_transit_buckets_dev(self.handle, C.byref(dev_segments.seg),
+                                                         None if dev_groups is None else C.c_void_p(dev_groups),
+                                                         C.byref(request), edges.ctypes.data_as(C.c_void_p), len(edges),
+                                                         C.c_void_p(dev_counts)))
+            counts[...] = self.download_array(dev_counts, counts.size, np.uint64).reshape(counts.shape)
+        finally:
+            self.dev_free(dev_counts)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return counts
+
+    def transit(self, batch, edges, groups=None, n_groups=None, max_gap=None):
+        """The transitions of `batch` as one bucket over its span, per group (shape (n_groups, len(edges) + 1,
+        len(edges) + 1), indexed [from][to]): the state-transition matrix of a whole batch."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(batch))])
+        n_cells = len(_edges_array(edges)) + 1
+        if len(batch) == 0:
+            return np.zeros((n_groups, n_cells, n_cells), dtype=np.uint64)
+        lo = int(min(np.min(batch.start_time), np.min(batch.end_time)))
+        hi = int(max(np.max(batch.start_time), np.max(batch.end_time)))
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the batch spans more than one bucket can hold: use transit_buckets")
+        return self.transit_buckets(batch, edges, lo, hi - lo + 1, 1, groups, max_gap, None, n_groups).reshape(
+            n_groups, n_cells, n_cells)
 
     # ---- sampling: the value of a series at regular instants (gap-fill, LOCF, interpolation) --------------------
 

@@ -61,24 +61,8 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_integral_heads(DevSegments s
     if (i == 0 || i >= s.n) return;
     if (offsets[i] == offsets[i - 1] || !integral_same_group(groups, i - 1, i)) return; // (never read)
     const SegInfo info = analyse_segment(s, i);
-    const SegDesc &d = info.desc;
     uint32_t error = info.error;
-    IntegralHead head = {0.0f, d.n_total};
-    if (!error && d.n_total > 0) {
-        const uint32_t type = d.flags & FLAG_TYPE_MASK;
-        if (type == MDB_MACAQUE_V_ID) {
-            const uint4 vv = s.values.views[i];
-            decode_macaque_v(view_data(s.values, i, vv), vv.x, 1u, false, 0, &error,
-                             [&](uint32_t, uint32_t bits) { head.value = __uint_as_float(bits); });
-        } else if (d.n_model > 0) {
-            head.value = model_value_at(d, type, d.start);
-        } else { // (a PMC-Mean segment whose every point is a residual)
-            const uint4 vr = s.residuals.views[i];
-            decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, 1u, true, __float_as_uint(d.value), &error,
-                             [&](uint32_t, uint32_t bits) { head.value = __uint_as_float(bits); });
-        }
-    }
-    heads[i] = head;
+    heads[i] = error ? IntegralHead{0.0f, info.desc.n_total} : integral_head_of(s, i, info, &error);
     if (error) atomicOr(error_out, error);
 }
 

@@ -275,6 +275,27 @@ __device__ __forceinline__ uint64_t integral_span(const DevSegments &s, const ui
     return bucket_span(s.start_time[i], integral_extent_end(s, groups, i, q.max_gap), q.buckets, first);
 }
 
+// The head of segment i, whose analysis is `info` (no error in it): its rows and, when it has any, its first value.
+// What k_integral_heads stores, shared with the heads kernel of mdb_transit.hip.
+__device__ __forceinline__ IntegralHead integral_head_of(const DevSegments &s, uint64_t i, const SegInfo &info, uint32_t *error) {
+    const SegDesc &d = info.desc;
+    IntegralHead head = {0.0f, d.n_total};
+    if (d.n_total == 0) return head;
+    const uint32_t type = d.flags & FLAG_TYPE_MASK;
+    if (type == MDB_MACAQUE_V_ID) {
+        const uint4 vv = s.values.views[i];
+        decode_macaque_v(view_data(s.values, i, vv), vv.x, 1u, false, 0, error,
+                         [&](uint32_t, uint32_t bits) { head.value = __uint_as_float(bits); });
+    } else if (d.n_model > 0) {
+        head.value = model_value_at(d, type, d.start);
+    } else { // (a PMC-Mean segment whose every point is a residual)
+        const uint4 vr = s.residuals.views[i];
+        decode_macaque_v(view_data(s.residuals, i, vr), vr.x - 1, 1u, true, __float_as_uint(d.value), error,
+                         [&](uint32_t, uint32_t bits) { head.value = __uint_as_float(bits); });
+    }
+    return head;
+}
+
 // Every row of segment i in row order: emit(t, v). `limit` rows at most on regular timestamps (the caller knows
 // how far its window reaches); irregular timestamps are decoded to the end. The walk of trend_stream_decode: the
 // values decoded once, the timestamp beside each.

@@ -39,6 +39,7 @@ pub use sys::{
     mdb_sample_cell as SampleCell, mdb_sample_request as SampleRequest,
     mdb_change_cell as ChangeCell, mdb_change_request as ChangeRequest,
     mdb_dwell_request as DwellRequest,
+    mdb_transit_request as TransitRequest,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
@@ -453,6 +454,35 @@ pub fn dwell_share(dwell: &[u64], n_cells: u32) -> Result<Vec<f64>> {
     let mut out = vec![0.0f64; dwell.len()];
     check(unsafe { sys::mdb_dwell_share(dwell.as_ptr(), (dwell.len() / n_cells as usize) as u64, n_cells, out.as_mut_ptr()) })?;
     Ok(out)
+}
+
+/// `into[k] += from[k]`: the merge of two counter arrays of `mdb_transit_buckets*` (host arithmetic, no GPU).
+pub fn transit_merge(into: &mut [u64], from: &[u64]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} counters merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_transit_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The pairs that went over each edge, per (group, bucket) row of `n_cells * n_cells` counters `[from][to]`: returns
+/// `(up, down)` with `n_cells - 1` entries per row, `up[e]` the sum of `counts[from <= e < to]` and `down[e]` the sum of
+/// `counts[to <= e < from]` (host arithmetic, no GPU). `counts.len()` must be a multiple of `n_cells * n_cells`.
+pub fn transit_crossings(counts: &[u64], n_cells: u32) -> Result<(Vec<u64>, Vec<u64>)> {
+    let matrix = n_cells as usize * n_cells as usize;
+    if n_cells == 0 || counts.len() % matrix != 0 {
+        return Err(HipError(format!("{} counters are no whole number of matrices of {} x {} cells", counts.len(), n_cells, n_cells)));
+    }
+    let n_rows = counts.len() / matrix;
+    let mut up = vec![0u64; n_rows * (n_cells as usize - 1)];
+    let mut down = vec![0u64; n_rows * (n_cells as usize - 1)];
+    check(unsafe { sys::mdb_transit_crossings(counts.as_ptr(), n_rows as u64, n_cells, up.as_mut_ptr(), down.as_mut_ptr()) })?;
+    Ok((up, down))
+}
+
+// The counters of mdb_transit_buckets*: n_groups * n_buckets matrices of (edges + 1)^2.
+fn check_transit_counts(request: &BucketRequest, n_edges: usize, n_counts: usize) -> Result<()> {
+    let n_cells = n_edges as u64 + 1;
+    check_hist_bucket_cells(request, n_cells.saturating_mul(n_cells), n_counts)
 }
 
 /// The time-weighted average `integral / duration` per cell, NaN where `duration == 0` (host arithmetic, no GPU).
@@ -1385,6 +1415,59 @@ impl Context {
         check(unsafe {
             sys::mdb_dwell_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
                                         request, edges.as_ptr(), n_edges, dwell.as_mut_ptr())
+        })
+    }
+
+    /// The linked pairs of rows of one field by the value cells they go from and to, per bucket of
+    /// `date_bin(width, ts, origin)` and group: `counts` is row-major `[n_groups][n_buckets][n_cells][n_cells]` with
+    /// `n_cells = edges.len() + 1`, indexed `[from][to]`, and the batch is ADDED to it. Rows are linked by the rule of
+    /// [`Context::integral_buckets`]; a pair belongs to the bucket of its later row, as in [`Context::change_buckets`];
+    /// the cells are those of [`Context::hist_buckets`]. [`transit_merge`] and [`transit_crossings`] apply.
+    pub fn transit_buckets(
+        &self,
+        segments: &SegmentsView,
+        group_of_segment: Option<&[u32]>,
+        request: &TransitRequest,
+        edges: &[f32],
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_transit_counts(&request.buckets, edges.len(), counts.len())?;
+        check_group_ids(segments, group_of_segment)?;
+        let groups = group_of_segment.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        check(unsafe {
+            sys::mdb_transit_buckets(self.raw(), &segments.raw, groups, request, edges.as_ptr(), n_edges, counts.as_mut_ptr())
+        })
+    }
+
+    /// [`Context::transit_buckets`] for several batches at once (rows in the order of the slice), folded as one batch:
+    /// a pair may cross from one batch to the next. `group_of_segment`: `None`, or one entry per batch (`None`: that
+    /// batch's rows in group 0).
+    pub fn transit_buckets_list(
+        &self,
+        segments: &[SegmentsView],
+        group_of_segment: Option<&[Option<&[u32]>]>,
+        request: &TransitRequest,
+        edges: &[f32],
+        counts: &mut [u64],
+    ) -> Result<()> {
+        check_transit_counts(&request.buckets, edges.len(), counts.len())?;
+        if let Some(groups) = group_of_segment {
+            if groups.len() != segments.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), segments.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(segments.len());
+        for (k, view) in segments.iter().enumerate() {
+            let groups = group_of_segment.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let n_edges = u32::try_from(edges.len()).unwrap_or(u32::MAX);
+        let inputs: Vec<*const sys::mdb_segments> = segments.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_transit_buckets_list(self.raw(), inputs.as_ptr(), group_pointers.as_ptr(), inputs.len() as u32,
+                                          request, edges.as_ptr(), n_edges, counts.as_mut_ptr())
         })
     }
 

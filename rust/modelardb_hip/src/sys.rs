@@ -483,6 +483,26 @@ const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, max_gap) == 48);
 const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, method) == 56);
 const _: () = assert!(std::mem::offset_of!(mdb_dwell_request, flags) == 60);
 
+/// The request of `mdb_transit_buckets*`. 64 bytes, laid out like `mdb_change_request`.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mdb_transit_request {
+    /// `t_lo` / `t_hi` must be `i64::MIN` / `i64::MAX` and `which_mask` 0: the buckets are the range.
+    pub buckets: mdb_bucket_request,
+    /// >= 0; `i64::MAX`: no gap rule.
+    pub max_gap: i64,
+    /// Must be 0.
+    pub reserved: u32,
+    /// Must be 0.
+    pub flags: u32,
+}
+
+const _: () = assert!(std::mem::size_of::<mdb_transit_request>() == 64);
+const _: () = assert!(std::mem::offset_of!(mdb_transit_request, buckets) == 0);
+const _: () = assert!(std::mem::offset_of!(mdb_transit_request, max_gap) == 48);
+const _: () = assert!(std::mem::offset_of!(mdb_transit_request, reserved) == 56);
+const _: () = assert!(std::mem::offset_of!(mdb_transit_request, flags) == 60);
+
 /// The statistics of `mdb_comoments_finish`; x is the independent variable: SQL's `regr_*(y, x)`.
 pub const MDB_COMOMENTS_COVAR_POP: u32 = 0;
 pub const MDB_COMOMENTS_COVAR_SAMP: u32 = 1;
@@ -717,6 +737,20 @@ unsafe extern "C" {
                                   dwell: *mut u64) -> c_int;
     pub fn mdb_dwell_merge_n(into: *mut u64, from: *const u64, n: u64) -> c_int;
     pub fn mdb_dwell_share(dwell: *const u64, n_rows: u64, n_cells: u32, out: *mut f64) -> c_int;
+
+    // ---- transitions between value cells, per bucket: starts per day, level crossings (include/mdb.h) ----
+    pub fn mdb_transit_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                               request: *const mdb_transit_request, edges: *const f32, n_edges: u32,
+                               counts: *mut u64) -> c_int;
+    pub fn mdb_transit_buckets_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
+                                   request: *const mdb_transit_request, edges: *const f32, n_edges: u32,
+                                   counts: *mut u64) -> c_int;
+    pub fn mdb_transit_buckets_list(ctx: *mut mdb_ctx, inputs: *const *const mdb_segments,
+                                    group_of_segment: *const *const u32, n_inputs: u32,
+                                    request: *const mdb_transit_request, edges: *const f32, n_edges: u32,
+                                    counts: *mut u64) -> c_int;
+    pub fn mdb_transit_merge_n(into: *mut u64, from: *const u64, n: u64) -> c_int;
+    pub fn mdb_transit_crossings(counts: *const u64, n_rows: u64, n_cells: u32, up: *mut u64, down: *mut u64) -> c_int;
     // ---- episodes: the maximal runs of points that pass a value predicate (include/mdb.h) ----
     pub fn mdb_episodes_count_dev(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                                   request: *const mdb_episodes_request, n_episodes: *mut u64, n_rows: *mut u64,
