@@ -292,4 +292,29 @@ __device__ __forceinline__ bool bucket_tail_by_pieces(const DevSegments &s, uint
 int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *rows, uint32_t n_inputs, uint64_t n,
                   const uint32_t **out);
 
+// mdb_buckets.hip: how every host form (a list of host batches, none of them NULL) gets onto the device. The object
+// takes the context's lock for as long as it lives; upload() selects the device and makes the list one device batch
+// (`transient`: into the context's upload scratch - else an upload the library holds, which gets the cursor index a
+// resident batch gets, so that the host and device forms decode the same streams the same way) with its group ids next
+// to it; the upload is freed on scope exit. upload_pair(): the operators over two fields - the y list as a batch of its
+// own, unless it is the x list (one pointer each, the same pointers), which is then uploaded once.
+class UploadedSegments {
+public:
+    explicit UploadedSegments(mdb_ctx *ctx) : lock_(ctx), ctx_(ctx) {}
+    ~UploadedSegments();
+    int upload(const mdb_segments *const *inputs, uint32_t n_inputs, const uint32_t *const *group_of_segment,
+               bool transient);
+    int upload_pair(const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys, uint32_t n_y,
+                    const uint32_t *const *group_of_segment_x);
+    const mdb_segments *segments() const;
+    const mdb_segments *y_segments() const; // (after upload_pair)
+    const uint32_t *groups() const { return groups_; }
+
+private:
+    CallGuard lock_;
+    mdb_ctx *ctx_;
+    mdb_segments_owned *dev_ = nullptr, *y_dev_ = nullptr;
+    const uint32_t *groups_ = nullptr;
+};
+
 } // namespace mdb

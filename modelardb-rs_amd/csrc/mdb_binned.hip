@@ -27,8 +27,10 @@
 //                           of a pair is the one the by_row selectors see: the segment's first row plus the number of
 //                           its earlier points inside [t_lo, t_hi].
 //   k_agg_bucket_check      (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_moments_tree / _fold  (mdb_moments.hip) runs of equal keys reduced through the fixed tree and merged into the
-//                           cell. No two lanes write one cell, no atomics on cells.
+//   k_moments_tree / _fold  the one tree and fold of every per-bucket operator (mdb_bucket_fold.hpp), instantiated here
+//                           with mdb_moments.hpp's MomentsFoldOps under the names mdb_moments.hip's launches have: runs
+//                           of equal keys reduced through the fixed tree and merged into the cell. No two lanes write
+//                           one cell, no atomics on cells.
 // Both walks are one function with two sinks, so they cut the same runs; a segment whose second walk does not produce
 // the number of runs its first walk counted fails the call (ERR_BINNED_RUNS) before anything is folded. Runs meet only
 // in moments_merge, in an order fixed by the input, the request, the edges and the slice size. The batch's cursor index
@@ -486,23 +488,12 @@ static int binned_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segments *
         return fail("A single segment of the x field has " + std::to_string(cap) + " runs, more than one slice can hold (" +
                     std::to_string(BUCKET_SLICE_MAX) + "): use fewer edges or cut the time range.");
     const uint64_t n_slices = cuts.size() - 1;
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    mdb_moments_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_moments_cell), &p)) return 1;
-        cells = static_cast<mdb_moments_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_moments_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(mdb_moments_cell), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    mdb_moments_cell *partials = pairs_scratch.take<mdb_moments_cell>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    MomentsTreeScratch tree_scratch;
-    if (moments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_moments_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<MomentsFoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    mdb_moments_cell *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         const uint64_t i0 = cuts[k], i1 = cuts[k + 1];
@@ -515,49 +506,23 @@ static int binned_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segments *
                                keys_dev, n_edges, slots.offsets, slots.slots, first_row, y, offsets, i0, i1, e0, partials,
                                keys, words);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (binned_error(read_back[0])) return 1;
-        if (moments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (binned_error(error)) return 1;
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_moments_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_moments_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int binned_list_run(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys, uint32_t n_y,
                     const uint32_t *const *group_of_segment_x, const mdb_bucket_request *request,
                     const std::vector<int32_t> &edge_keys, uint64_t n_cells, mdb_moments_cell *inout) {
-    std::vector<uint64_t> rows(n_x);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_x; k++) {
-        rows[k] = xs[k]->n;
-        n += rows[k];
-    }
-    // (the same list on both sides - one pointer each, the same pointer - is uploaded once)
-    bool same = n_x == n_y;
-    for (uint32_t k = 0; same && k < n_x; k++) same = xs[k] == ys[k];
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (uploads the library holds, as mdb_comoments_buckets_list: two batches are alive at once)
-    mdb_segments_owned *x_dev = nullptr, *y_dev = nullptr;
-    if (upload_segment_list_locked(ctx, xs, n_x, false, &x_dev)) return 1;
-    int rc = same ? 0 : upload_segment_list_locked(ctx, ys, n_y, false, &y_dev);
-    const uint32_t *groups = nullptr;
-    if (!rc) rc = upload_groups(ctx, group_of_segment_x, rows.data(), n_x, n, &groups);
-    if (!rc)
-        rc = binned_run(ctx, &x_dev->seg, same ? &x_dev->seg : &y_dev->seg, groups, request, edge_keys, n_cells, nullptr, inout);
-    if (y_dev) mdb_segments_free(y_dev);
-    mdb_segments_free(x_dev);
-    return rc;
+    UploadedSegments lists(ctx);
+    if (lists.upload_pair(xs, n_x, ys, n_y, group_of_segment_x)) return 1;
+    return binned_run(ctx, lists.segments(), lists.y_segments(), lists.groups(), request, edge_keys, n_cells, nullptr,
+                      inout);
 }
 
 } // namespace mdb

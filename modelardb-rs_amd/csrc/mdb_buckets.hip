@@ -20,13 +20,17 @@
 //                          the entries are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check     are the keys non-decreasing in pair order (ModelarDB's storage order: segments by tags, then
 //                          start_time, groups following the tags)? If not, a stable radix sort by key (rocPRIM).
-//   k_agg_bucket_tree      runs of equal keys reduced through a fixed tree of 64-entry tiles: level l+1 holds, per
-//                          tile of level l, its last key and the fold of the run that ends the tile.
-//   k_agg_bucket_fold      1 lane / pair: the lane of a run's last pair folds the run (its tile, then one tile's
-//                          entry per level up) and merges it into the cell - no two lanes write one cell, no float
-//                          atomics, the order of every addition fixed by the pair order: run-to-run deterministic.
+//   k_agg_bucket_tree      (k_bucket_tree<AggFoldOps>) runs of equal keys reduced through a fixed tree of 64-entry
+//                          tiles: level l+1 holds, per tile of level l, its last key and the fold of the run that ends
+//                          the tile.
+//   k_agg_bucket_fold      (k_bucket_fold<AggFoldOps>) 1 lane / pair: the lane of a run's last pair folds the run (its
+//                          tile, then one tile's entry per level up) and merges it into the cell - no two lanes write
+//                          one cell, no float atomics, the order of every addition fixed by the pair order: run-to-run
+//                          deterministic.
+// The tree and the fold are one template for every per-bucket operator (mdb_bucket_fold.hpp: the two kernels, the
+// scratch of a slice, the working copy of the cells); what is the aggregates' own is AggFoldOps below.
 // Bytes (Swing on regular timestamps): ~70 B of metadata per segment read, 32 B per pair written and read back.
-#include "mdb_buckets.hpp"
+#include "mdb_bucket_fold.hpp"
 #include "mdb_scan.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -37,14 +41,6 @@
 #include <vector>
 
 namespace mdb {
-
-struct BucketTree { // level 0 is the slice's pairs (keys, partials, and the sort's pair numbers); 1.. are the tree's
-    const unsigned long long *keys[BUCKET_MAX_LEVELS];
-    const BucketPartial *values[BUCKET_MAX_LEVELS];
-    uint64_t n[BUCKET_MAX_LEVELS];
-    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
-    int levels;
-};
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_span(DevSegments s, const uint32_t *__restrict__ groups,
                                                                     BucketRequest r,
@@ -218,65 +214,23 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_iota(uint32_t *__
     if (j < n) out[j] = (uint32_t)j;
 }
 
-__device__ __forceinline__ BucketPartial bucket_value(const BucketTree &tree, int level, uint64_t t) {
-    return tree.values[level][level == 0 && tree.order ? tree.order[t] : t];
-}
-
-// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the fold of the run ending it.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_tree(BucketTree tree, int level,
-                                                                    unsigned long long *__restrict__ keys_out,
-                                                                    BucketPartial *__restrict__ values_out) {
-    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[level];
-    const uint64_t first = u * BUCKET_TILE;
-    if (first >= n) return;
-    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
-    const unsigned long long *keys = tree.keys[level];
-    const unsigned long long key = keys[last];
-    BucketPartial acc = bucket_value(tree, level, last);
-    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) bucket_add(acc, bucket_value(tree, level, t - 1));
-    keys_out[u] = key;
-    values_out[u] = acc;
-}
-
-// The lane of the last pair of each run of equal keys folds the run and merges it into its cell (mdb_agg_merge's
-// rules, for the aggregates in which_mask); a run without points leaves the cell alone.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_agg_bucket_fold(BucketTree tree, uint32_t which_mask,
-                                                                    mdb_agg_state *__restrict__ cells) {
-    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[0];
-    if (j >= n) return;
-    const unsigned long long key = tree.keys[0][j];
-    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
-    BucketPartial acc = bucket_empty();
-    uint64_t index = j;
-    for (int level = 0; level < tree.levels; level++) {
-        const uint64_t first = index - index % BUCKET_TILE;
-        const unsigned long long *keys = tree.keys[level];
-        uint64_t t = index;
-        bool whole = true; // every entry from `first` to `index` belongs to the run
-        while (true) {
-            if (keys[t] != key) {
-                whole = false;
-                break;
-            }
-            bucket_add(acc, bucket_value(tree, level, t));
-            if (t == first) break;
-            t--;
-        }
-        if (!whole || first == 0) break;
-        index = first / BUCKET_TILE - 1; // the tile in front, one level up
+// What the tree and fold (mdb_bucket_fold.hpp) need to know of the aggregates: a run enters its cell by mdb_agg_merge's
+// rules, for the aggregates in which_mask.
+struct AggFoldOps : FoldOps<BucketPartial, mdb_agg_state> {
+    static constexpr const char *tree_name = "k_agg_bucket_tree", *fold_name = "k_agg_bucket_fold";
+    uint32_t which_mask;
+    __device__ __forceinline__ static BucketPartial empty() { return bucket_empty(); }
+    __device__ __forceinline__ static void merge(BucketPartial &into, const BucketPartial &from) { bucket_add(into, from); }
+    __device__ __forceinline__ static bool is_empty(const BucketPartial &acc) { return acc.count == 0; }
+    __device__ __forceinline__ void apply(mdb_agg_state &cell, const BucketPartial &acc) const {
+        if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) cell.count += acc.count;
+        if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) cell.sum += acc.sum;
+        if ((which_mask & MDB_AGG_MIN) && !(acc.min != acc.min) && (cell.min != cell.min || acc.min < cell.min))
+            cell.min = acc.min;
+        if ((which_mask & MDB_AGG_MAX) && !(acc.max != acc.max) && (cell.max != cell.max || acc.max > cell.max))
+            cell.max = acc.max;
     }
-    if (acc.count == 0) return;
-    mdb_agg_state cell = cells[key];
-    if (which_mask & (MDB_AGG_COUNT | MDB_AGG_AVG)) cell.count += acc.count;
-    if (which_mask & (MDB_AGG_SUM | MDB_AGG_AVG)) cell.sum += acc.sum;
-    if ((which_mask & MDB_AGG_MIN) && !(acc.min != acc.min) && (cell.min != cell.min || acc.min < cell.min))
-        cell.min = acc.min;
-    if ((which_mask & MDB_AGG_MAX) && !(acc.max != acc.max) && (cell.max != cell.max || acc.max > cell.max))
-        cell.max = acc.max;
-    cells[key] = cell;
-}
+};
 
 // ---- the pieces of MacaqueV streams ----------------------------------------------------------------------------
 // The streams bucket_values_by_pieces / bucket_tail_by_pieces take (regular timestamps: point k at start + k delta)
@@ -459,6 +413,18 @@ void bucket_keys_check(mdb_ctx *ctx, const unsigned long long *keys, uint64_t m,
                        unsorted);
 }
 
+int bucket_slice_check(mdb_ctx *ctx, const unsigned long long *keys, uint64_t m, unsigned int *words,
+                       unsigned int *error, bool *unsorted) {
+    bucket_keys_check(ctx, keys, m, words + 1);
+    unsigned int read_back[2] = {0, 0};
+    MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
+    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MDB_HIP_CHECK(hipGetLastError());
+    *error = read_back[0];
+    *unsorted = read_back[1] != 0;
+    return 0;
+}
+
 int bucket_keys_sort(mdb_ctx *ctx, unsigned long long *keys, uint64_t m, unsigned int key_bits,
                      const unsigned long long **sorted_out, const uint32_t **order_out) {
     void *p;
@@ -520,7 +486,6 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
     unsigned long long total = 0;
     if (bucket_span_pairs(ctx, in, s, groups, r, &offsets, &words, &total)) return 1;
     if (total == 0) return 0;
-    void *p;
     // The MacaqueV streams of the batch's cursor index (built here for a batch the library holds; MDB_GRID_MV_INDEX=0:
     // none) go piece by piece: their entries are folded behind the pairs, in slices of their own.
     std::shared_ptr<MvIndex> index;
@@ -533,35 +498,12 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
     const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
     const uint64_t n_slices = pair_slices + entry_slices;
     const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    mdb_agg_state *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_agg_state), &p)) return 1;
-        cells = static_cast<mdb_agg_state *>(p);
-        if (host_cells)
-            MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells, n_cells * sizeof(mdb_agg_state), hipMemcpyHostToDevice,
-                                         ctx->stream));
-        else
-            MDB_HIP_CHECK(hipMemcpyAsync(cells, dev_cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToDevice,
-                                         ctx->stream));
-    }
-    const uint64_t partials_bytes = align_up(cap * sizeof(BucketPartial), 256);
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, partials_bytes + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    BucketPartial *partials = pairs_scratch.take<BucketPartial>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries.
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(BucketPartial)) + 256, &p)) return 1;
-    unsigned long long *tree_keys = static_cast<unsigned long long *>(p);
-    BucketPartial *tree_values = reinterpret_cast<BucketPartial *>(tree_keys + tree_entries);
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_agg_state> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<AggFoldOps> fold(AggFoldOps{{}, r.which_mask});
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    BucketPartial *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         // (slices of pairs first, then slices of the pieces' entries)
@@ -582,55 +524,13 @@ int buckets_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
                                          filter)) {
             return 1;
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        BucketTree tree = {};
-        tree.keys[0] = keys;
-        tree.values[0] = partials;
-        tree.n[0] = m;
-        tree.order = nullptr;
-        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-        }
-        // The tree's levels over this slice, then the fold.
-        tree.levels = 1;
-        uint64_t used = 0;
-        {
-            LaunchTimer timer(ctx, "k_agg_bucket_tree");
-            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-                unsigned long long *level_keys = tree_keys + used;
-                BucketPartial *level_values = tree_values + used;
-                hipLaunchKernelGGL(k_agg_bucket_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                                   tree.levels - 1, level_keys, level_values);
-                tree.keys[tree.levels] = level_keys;
-                tree.values[tree.levels] = level_values;
-                tree.n[tree.levels] = up;
-                used += up + 1;
-                size = up;
-            }
-        }
-        {
-            LaunchTimer timer(ctx, "k_agg_bucket_fold");
-            hipLaunchKernelGGL(k_agg_bucket_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                               r.which_mask, cells);
-        }
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToHost,
-                                     ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_agg_state), hipMemcpyDeviceToDevice,
-                                     ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 // The host-side checks of the filtered forms, before the device is used: the request's and the filter's own, then the
@@ -667,29 +567,56 @@ int upload_groups(mdb_ctx *ctx, const uint32_t *const *groups, const uint64_t *r
     return 0;
 }
 
+UploadedSegments::~UploadedSegments() {
+    if (y_dev_) mdb_segments_free(y_dev_);
+    if (dev_) mdb_segments_free(dev_);
+}
+
+const mdb_segments *UploadedSegments::segments() const { return &dev_->seg; }
+const mdb_segments *UploadedSegments::y_segments() const { return y_dev_ ? &y_dev_->seg : &dev_->seg; }
+
+static int upload_list_groups(mdb_ctx *ctx, const mdb_segments *const *inputs, uint32_t n_inputs,
+                              const uint32_t *const *group_of_segment, const uint32_t **groups) {
+    std::vector<uint64_t> rows(n_inputs);
+    uint64_t n = 0;
+    for (uint32_t k = 0; k < n_inputs; k++) {
+        rows[k] = inputs[k]->n;
+        n += rows[k];
+    }
+    return upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, groups);
+}
+
+int UploadedSegments::upload(const mdb_segments *const *inputs, uint32_t n_inputs,
+                             const uint32_t *const *group_of_segment, bool transient) {
+    MDB_HIP_CHECK(hipSetDevice(ctx_->device));
+    if (upload_segment_list_locked(ctx_, inputs, n_inputs, transient, &dev_)) return 1;
+    return upload_list_groups(ctx_, inputs, n_inputs, group_of_segment, &groups_);
+}
+
+int UploadedSegments::upload_pair(const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys, uint32_t n_y,
+                                  const uint32_t *const *group_of_segment_x) {
+    bool same = n_x == n_y;
+    for (uint32_t k = 0; same && k < n_x; k++) same = xs[k] == ys[k];
+    MDB_HIP_CHECK(hipSetDevice(ctx_->device));
+    // (uploads the library holds: two batches are alive at once)
+    if (upload_segment_list_locked(ctx_, xs, n_x, false, &dev_)) return 1;
+    if (!same && upload_segment_list_locked(ctx_, ys, n_y, false, &y_dev_)) return 1;
+    return upload_list_groups(ctx_, xs, n_x, group_of_segment_x, &groups_);
+}
+
 // (the host forms of both calls: `filter` nullptr for mdb_agg_buckets*, else the folded keys and narrowed request)
 static int buckets_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                             uint32_t n_inputs, const mdb_bucket_request *request, uint64_t n_cells,
                             const ValueKeys *filter, mdb_agg_state *inout) {
-    std::vector<uint64_t> rows(n_inputs);
     uint64_t n = 0;
     for (uint32_t k = 0; k < n_inputs; k++) {
         if (!inputs[k]) return fail("A batch of the list is NULL.");
-        rows[k] = inputs[k]->n;
-        n += rows[k];
+        n += inputs[k]->n;
     }
     if (n == 0 || request->n_buckets == 0) return 0;
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    // (an upload the library holds, not its transient scratch: the batch then gets the cursor index a resident batch
-    // gets, and the host and device forms decode the same streams the same way - bit-identical results)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = buckets_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout, filter);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, false)) return 1;
+    return buckets_run(ctx, list.segments(), list.groups(), request, n_cells, nullptr, inout, filter);
 }
 
 } // namespace mdb

@@ -2,7 +2,8 @@
 // arithmetic: mdb_buckets.hip (COUNT / MIN / MAX / SUM per bucket) and mdb_m4.hip (first / last / min / max points per
 // bucket). The sizes of the pair machinery, the visible values of a piece of an indexed MacaqueV stream, and the host
 // steps that do not depend on what a partial holds (the span and its scan, the entry counts of the pieces, the sort of
-// the keys): defined in mdb_buckets.hip.
+// the keys, the check of a slice): defined in mdb_buckets.hip. What does depend on the partial - the reduction tree and
+// the fold - is one template over it: mdb_bucket_fold.hpp.
 #pragma once
 
 #include "mdb_agg_dev.hpp"
@@ -77,6 +78,12 @@ int bucket_pieces_count(mdb_ctx *ctx, const DevSegments &s, const BucketRequest 
 
 // k_agg_bucket_check: *unsorted |= 1 if the m keys are not non-decreasing.
 void bucket_keys_check(mdb_ctx *ctx, const unsigned long long *keys, uint64_t m, unsigned int *unsorted);
+
+// The step between an operator's partials kernels and the fold of a slice (mdb_bucket_fold.hpp): the m keys checked,
+// the two read-back words fetched (words[0]: the error bits the operator's kernels ORed, words[1]: the check's flag)
+// and the stream synchronised. The caller makes its own message of *error.
+int bucket_slice_check(mdb_ctx *ctx, const unsigned long long *keys, uint64_t m, unsigned int *words, unsigned int *error,
+                       bool *unsorted);
 
 // The sort path: the m keys in order (stable, rocPRIM's radix sort over key_bits bits) and the pair numbers alongside,
 // both in scratch.

@@ -23,9 +23,12 @@
 //   k_comoments_pieces     1 lane / piece of 64 values, one entry {key, cell} per bucket the piece reaches; the entries
 //                          are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check     (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_comoments_tree       runs of equal keys reduced through a fixed tree of 64-entry tiles.
-//   k_comoments_fold       1 lane / pair: the lane of a run's last pair folds the run and merges it into the cell. No
-//                          two lanes write one cell, no atomics on cells.
+//   k_comoments_tree       (k_bucket_tree<ComomentsFoldOps>) runs of equal keys reduced through a fixed tree of 64-entry
+//                          tiles.
+//   k_comoments_fold       (k_bucket_fold<ComomentsFoldOps>) 1 lane / pair: the lane of a run's last pair folds the run
+//                          and merges it into the cell. No two lanes write one cell, no atomics on cells.
+// The tree and the fold are the one template of every per-bucket operator (mdb_bucket_fold.hpp), instantiated with
+// ComomentsFoldOps (mdb_comoments.hpp).
 // The row of a point is its segment's first row plus the number of the segment's earlier points inside [t_lo, t_hi]:
 // what segment_range (mdb_agg_dev.hpp) calls the row of a point and the mask consumers test a bit at.
 // Every run is summed around its first pair (mdb_comoments.hpp) and runs meet only in comoments_merge, in an order fixed
@@ -38,17 +41,8 @@
 
 #include <algorithm>
 #include <string>
-#include <vector>
 
 namespace mdb {
-
-struct ComomentsTree { // level 0 is the slice's pairs (keys, cells, and the sort's pair numbers); 1.. are the tree's
-    const unsigned long long *keys[BUCKET_MAX_LEVELS];
-    const mdb_comoments_cell *values[BUCKET_MAX_LEVELS];
-    uint64_t n[BUCKET_MAX_LEVELS];
-    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
-    int levels;
-};
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_comoments_partials(
     DevSegments s, const uint32_t *__restrict__ groups, BucketRequest r, const unsigned long long *__restrict__ offsets,
@@ -92,60 +86,6 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_comoments_partials(
         }
     }
     if (error) atomicOr(error_out, error);
-}
-
-__device__ __forceinline__ mdb_comoments_cell comoments_value(const ComomentsTree &tree, int level, uint64_t t) {
-    return tree.values[level][level == 0 && tree.order ? tree.order[t] : t];
-}
-
-// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the fold of the run ending it.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_comoments_tree(ComomentsTree tree, int level,
-                                                                   unsigned long long *__restrict__ keys_out,
-                                                                   mdb_comoments_cell *__restrict__ values_out) {
-    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[level];
-    const uint64_t first = u * BUCKET_TILE;
-    if (first >= n) return;
-    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
-    const unsigned long long *keys = tree.keys[level];
-    const unsigned long long key = keys[last];
-    mdb_comoments_cell acc = comoments_value(tree, level, last);
-    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) comoments_merge(acc, comoments_value(tree, level, t - 1));
-    keys_out[u] = key;
-    values_out[u] = acc;
-}
-
-// The lane of the last pair of each run of equal keys folds the run and merges it into its cell; a run without points
-// leaves the cell alone.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_comoments_fold(ComomentsTree tree, mdb_comoments_cell *__restrict__ cells) {
-    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[0];
-    if (j >= n) return;
-    const unsigned long long key = tree.keys[0][j];
-    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
-    mdb_comoments_cell acc = comoments_empty();
-    uint64_t index = j;
-    for (int level = 0; level < tree.levels; level++) {
-        const uint64_t first = index - index % BUCKET_TILE;
-        const unsigned long long *keys = tree.keys[level];
-        uint64_t t = index;
-        bool whole = true; // every entry from `first` to `index` belongs to the run
-        while (true) {
-            if (keys[t] != key) {
-                whole = false;
-                break;
-            }
-            comoments_merge(acc, comoments_value(tree, level, t));
-            if (t == first) break;
-            t--;
-        }
-        if (!whole || first == 0) break;
-        index = first / BUCKET_TILE - 1; // the tile in front, one level up
-    }
-    if (acc.count == 0) return;
-    mdb_comoments_cell cell = cells[key];
-    comoments_merge(cell, acc);
-    cells[key] = cell;
 }
 
 // The pieces of the MacaqueV streams bucket_values_by_pieces / bucket_tail_by_pieces take, as k_moments_pieces: one
@@ -221,56 +161,6 @@ __global__ __launch_bounds__(MDB_WAVE) void k_comoments_pieces(
     if (error) atomicOr(error_out, error);
 }
 
-int comoments_tree_reserve(mdb_ctx *ctx, uint64_t cap, ComomentsTreeScratch *out) {
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    void *p;
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_comoments_cell)) + 256, &p)) return 1;
-    out->values = static_cast<mdb_comoments_cell *>(p);
-    out->keys = reinterpret_cast<unsigned long long *>(out->values + tree_entries);
-    return 0;
-}
-
-int comoments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_comoments_cell *partials, uint64_t m,
-                         bool unsorted, unsigned int key_bits, const ComomentsTreeScratch &scratch,
-                         mdb_comoments_cell *cells) {
-    ComomentsTree tree = {};
-    tree.keys[0] = keys;
-    tree.values[0] = partials;
-    tree.n[0] = m;
-    tree.order = nullptr;
-    if (unsorted) { // keys out of order: a stable sort by key, pair numbers alongside
-        if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-    }
-    // The tree's levels over this slice, then the fold.
-    tree.levels = 1;
-    uint64_t used = 0;
-    {
-        LaunchTimer timer(ctx, "k_comoments_tree");
-        for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-            const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-            unsigned long long *level_keys = scratch.keys + used;
-            mdb_comoments_cell *level_values = scratch.values + used;
-            hipLaunchKernelGGL(k_comoments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                               tree.levels - 1, level_keys, level_values);
-            tree.keys[tree.levels] = level_keys;
-            tree.values[tree.levels] = level_values;
-            tree.n[tree.levels] = up;
-            used += up + 1;
-            size = up;
-        }
-    }
-    {
-        LaunchTimer timer(ctx, "k_comoments_fold");
-        hipLaunchKernelGGL(k_comoments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-    }
-    return 0;
-}
-
 // The rows of x and y under [t_lo, t_hi] compared, x's first rows (n + 1, in SCRATCH_COMOMENTS_ROWS: a slot of its
 // own, the range grid of y and the row masks use theirs meanwhile) and the y column (SCRATCH_COMOMENTS_YCOL).
 int comoments_rows(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, int64_t t_lo, int64_t t_hi,
@@ -340,24 +230,12 @@ static int comoments_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segment
     const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
     const uint64_t n_slices = pair_slices + entry_slices;
     const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    void *p;
-    mdb_comoments_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_comoments_cell), &p)) return 1;
-        cells = static_cast<mdb_comoments_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_comoments_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(mdb_comoments_cell), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    mdb_comoments_cell *partials = pairs_scratch.take<mdb_comoments_cell>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    ComomentsTreeScratch tree_scratch;
-    if (comoments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_comoments_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<ComomentsFoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    mdb_comoments_cell *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         // (slices of pairs first, then slices of the pieces' entries)
@@ -377,52 +255,25 @@ static int comoments_run(mdb_ctx *ctx, const mdb_segments *in, const mdb_segment
                                (unsigned long long)n_pieces, entry_offsets, p0, p1, keys, partials, first_row, y,
                                words);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0] & ERR_COMOMENTS_ROW)
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error & ERR_COMOMENTS_ROW)
             return fail("(internal) A row of the x field lies beyond the y column: the row plan and the range grid "
                         "disagree.");
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        if (comoments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_comoments_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_comoments_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int comoments_list_run(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys,
                        uint32_t n_y, const uint32_t *const *group_of_segment_x, const mdb_bucket_request *request,
                        uint64_t n_cells, mdb_comoments_cell *inout) {
-    std::vector<uint64_t> rows(n_x);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_x; k++) {
-        rows[k] = xs[k]->n;
-        n += rows[k];
-    }
-    // (the same list on both sides - one pointer each, the same pointer - is uploaded once)
-    bool same = n_x == n_y;
-    for (uint32_t k = 0; same && k < n_x; k++) same = xs[k] == ys[k];
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (uploads the library holds, as mdb_moments_buckets_list: the batches get the cursor index a resident batch gets)
-    mdb_segments_owned *x_dev = nullptr, *y_dev = nullptr;
-    if (upload_segment_list_locked(ctx, xs, n_x, false, &x_dev)) return 1;
-    int rc = same ? 0 : upload_segment_list_locked(ctx, ys, n_y, false, &y_dev);
-    const uint32_t *groups = nullptr;
-    if (!rc) rc = upload_groups(ctx, group_of_segment_x, rows.data(), n_x, n, &groups);
-    if (!rc) rc = comoments_run(ctx, &x_dev->seg, same ? &x_dev->seg : &y_dev->seg, groups, request, n_cells, nullptr, inout);
-    if (y_dev) mdb_segments_free(y_dev);
-    mdb_segments_free(x_dev);
-    return rc;
+    UploadedSegments lists(ctx);
+    if (lists.upload_pair(xs, n_x, ys, n_y, group_of_segment_x)) return 1;
+    return comoments_run(ctx, lists.segments(), lists.y_segments(), lists.groups(), request, n_cells, nullptr, inout);
 }
 
 } // namespace mdb

@@ -128,18 +128,15 @@ namespace mdb {
 
 __device__ __forceinline__ mdb_comoments_cell comoments_empty() { return mdb_comoments_cell{0, 0.0, 0.0, 0.0, 0.0, 0.0}; }
 
-// mdb_comoments.hip, for the operators whose partials are comoments cells (mdb_trend.hip too), as moments_tree_reserve /
-// moments_fold_slice (mdb_moments.hpp): the upper levels of the reduction tree over slices of at most `cap` entries
-// (SCRATCH_BUCKET_TREE), and one slice folded - the m entries {keys[j], partials[j]} reduced by k_comoments_tree and
-// merged into cells[key] by k_comoments_fold, enqueued on the context's stream.
-struct ComomentsTreeScratch {
-    mdb_comoments_cell *values;
-    unsigned long long *keys;
+// What the tree and fold (mdb_bucket_fold.hpp) need to know of a comoments cell: for mdb_comoments.hip and for
+// mdb_trend.hip, whose partials are comoments cells too (each instantiates BucketFold<ComomentsFoldOps> itself).
+struct ComomentsFoldOps : FoldOps<mdb_comoments_cell> {
+    static constexpr const char *tree_name = "k_comoments_tree", *fold_name = "k_comoments_fold";
+    __device__ __forceinline__ static mdb_comoments_cell empty() { return comoments_empty(); }
+    __device__ __forceinline__ static void merge(mdb_comoments_cell &into, const mdb_comoments_cell &from) { comoments_merge(into, from); }
+    __device__ __forceinline__ static bool is_empty(const mdb_comoments_cell &acc) { return acc.count == 0; }
+    __device__ __forceinline__ void apply(mdb_comoments_cell &cell, const mdb_comoments_cell &acc) const { comoments_merge(cell, acc); }
 };
-int comoments_tree_reserve(mdb_ctx *ctx, uint64_t cap, ComomentsTreeScratch *out);
-int comoments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_comoments_cell *partials, uint64_t m,
-                         bool unsorted, unsigned int key_bits, const ComomentsTreeScratch &scratch,
-                         mdb_comoments_cell *cells);
 
 // The y column: one f32 per row of the range grid of the y field. The row of point k of an x segment is `base` + k,
 // where base = the segment's first row - the index of its first point inside [t_lo, t_hi] (wrapping arithmetic: the

@@ -108,22 +108,10 @@ int dwell_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, cons
 int dwell_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                    uint32_t n_inputs, const mdb_dwell_request *request, const std::vector<int32_t> &edge_keys,
                    uint64_t n_rows, uint64_t *dwell) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (into the context's upload scratch, as mdb_hist_buckets_list: the host and device forms run the same kernel)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = dwell_run(ctx, &dev->seg, groups, request, edge_keys, n_rows, nullptr, dwell);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, true)) return 1;
+    return dwell_run(ctx, list.segments(), list.groups(), request, edge_keys, n_rows, nullptr, dwell);
 }
 
 } // namespace mdb

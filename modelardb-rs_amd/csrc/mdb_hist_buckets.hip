@@ -547,23 +547,15 @@ int mdb_hist_buckets_list(mdb_ctx *ctx, const mdb_segments *const *inputs, const
     uint64_t n_rows = 0;
     if (hist_edge_keys(edges, n_edges, &edge_keys)) return 1;
     if (hist_buckets_request_check(request, (uint64_t)n_edges + 1, "mdb_hist_buckets*", &n_rows)) return 1;
-    std::vector<uint64_t> rows(n_inputs);
     uint64_t n = 0;
     for (uint32_t k = 0; k < n_inputs; k++) {
         if (!inputs[k]) return fail("A batch of the list is NULL.");
-        rows[k] = inputs[k]->n;
-        n += rows[k];
+        n += inputs[k]->n;
     }
     if (n == 0 || n_rows == 0) return 0;
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = hist_buckets_run(ctx, &dev->seg, groups, request, edge_keys, n_rows, nullptr, counts);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, true)) return 1;
+    return hist_buckets_run(ctx, list.segments(), list.groups(), request, edge_keys, n_rows, nullptr, counts);
 }
 
 int mdb_hist_buckets(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group_of_segment,

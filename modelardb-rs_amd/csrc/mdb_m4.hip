@@ -3,7 +3,8 @@
 //
 // What the reference answers with GridExec -> AggregateExec(first_value / last_value ORDER BY ts, min, max) and a join
 // back onto the points for the timestamps of the extremes. The structure is that of mdb_buckets.hip, whose span, scan,
-// key check and sort are shared (mdb_buckets.hpp); the partial carries four points instead of four numbers:
+// key check and sort are shared (mdb_buckets.hpp), as are the reduction tree and the fold - one template for every
+// per-bucket operator (mdb_bucket_fold.hpp, M4FoldOps below); the partial carries four points instead of four numbers:
 //
 //   k_agg_bucket_span   (shared) the buckets each segment reaches, its group id checked; a scan makes pair offsets.
 //   then per slice of at most MDB_AGG_BUCKET_SLICE_PAIRS pairs, slices folded one after the other:
@@ -15,9 +16,9 @@
 //   k_m4_pieces         1 lane / piece of 64 values, one entry {key, record} per bucket the piece reaches; the entries
 //                       are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check  (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_m4_tree           runs of equal keys reduced through a fixed tree of 64-entry tiles.
-//   k_m4_fold           1 lane / pair: the lane of a run's last pair folds the run and merges it into the cell. No two
-//                       lanes write one cell, no atomics on cells.
+//   k_m4_tree           (k_bucket_tree<M4FoldOps>) runs of equal keys reduced through a fixed tree of 64-entry tiles.
+//   k_m4_fold           (k_bucket_fold<M4FoldOps>) 1 lane / pair: the lane of a run's last pair folds the run and merges
+//                       it into the cell. No two lanes write one cell, no atomics on cells.
 // The four rules are minima under total orders (mdb_m4.hpp), so the bytes of a cell do not depend on the order in
 // which anything above happens.
 //
@@ -25,20 +26,23 @@
 // four 16-byte words - not split arrays: a lane writes the records of ITS segment's pairs one after the other, so
 // the words of one record are what lies together in memory, and a record is one 64-byte sector. With the 8-byte key:
 // 72 B per pair written and read back (mdb_agg_buckets: 24 + 8).
+#include "mdb_bucket_fold.hpp"
 #include "mdb_m4.hpp"
 #include "mdb_scan.hpp"
 
 #include <algorithm>
-#include <vector>
 
 namespace mdb {
 
-struct M4Tree { // level 0 is the slice's pairs (keys, records, and the sort's pair numbers); 1.. are the tree's
-    const unsigned long long *keys[BUCKET_MAX_LEVELS];
-    const M4Partial *values[BUCKET_MAX_LEVELS];
-    uint64_t n[BUCKET_MAX_LEVELS];
-    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
-    int levels;
+// What the tree and fold (mdb_bucket_fold.hpp) need to know of a record: its four 16-byte words, the four rules.
+struct M4FoldOps : FoldOps<M4Partial, mdb_m4_cell> {
+    static constexpr const char *tree_name = "k_m4_tree", *fold_name = "k_m4_fold";
+    __device__ __forceinline__ static M4Partial load(const M4Partial *from) { return m4_load(from); }
+    __device__ __forceinline__ static void store(M4Partial *to, const M4Partial &value) { m4_store(to, value); }
+    __device__ __forceinline__ static M4Partial empty() { return m4_empty(); }
+    __device__ __forceinline__ static void merge(M4Partial &into, const M4Partial &from) { m4_merge(into, from); }
+    __device__ __forceinline__ static bool is_empty(const M4Partial &acc) { return acc.count == 0; }
+    __device__ __forceinline__ void apply(mdb_m4_cell &cell, const M4Partial &acc) const { m4_merge(cell, acc); }
 };
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_m4_partials(DevSegments s, const uint32_t *__restrict__ groups,
@@ -83,60 +87,6 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_m4_partials(DevSegments s, c
         }
     }
     if (error) atomicOr(error_out, error);
-}
-
-__device__ __forceinline__ M4Partial m4_value(const M4Tree &tree, int level, uint64_t t) {
-    return m4_load(&tree.values[level][level == 0 && tree.order ? tree.order[t] : t]);
-}
-
-// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the fold of the run ending it.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_m4_tree(M4Tree tree, int level,
-                                                            unsigned long long *__restrict__ keys_out,
-                                                            M4Partial *__restrict__ values_out) {
-    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[level];
-    const uint64_t first = u * BUCKET_TILE;
-    if (first >= n) return;
-    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
-    const unsigned long long *keys = tree.keys[level];
-    const unsigned long long key = keys[last];
-    M4Partial acc = m4_value(tree, level, last);
-    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) m4_merge(acc, m4_value(tree, level, t - 1));
-    keys_out[u] = key;
-    m4_store(&values_out[u], acc);
-}
-
-// The lane of the last pair of each run of equal keys folds the run and merges it into its cell; a run without points
-// leaves the cell alone.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_m4_fold(M4Tree tree, mdb_m4_cell *__restrict__ cells) {
-    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[0];
-    if (j >= n) return;
-    const unsigned long long key = tree.keys[0][j];
-    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
-    M4Partial acc = m4_empty();
-    uint64_t index = j;
-    for (int level = 0; level < tree.levels; level++) {
-        const uint64_t first = index - index % BUCKET_TILE;
-        const unsigned long long *keys = tree.keys[level];
-        uint64_t t = index;
-        bool whole = true; // every entry from `first` to `index` belongs to the run
-        while (true) {
-            if (keys[t] != key) {
-                whole = false;
-                break;
-            }
-            m4_merge(acc, m4_value(tree, level, t));
-            if (t == first) break;
-            t--;
-        }
-        if (!whole || first == 0) break;
-        index = first / BUCKET_TILE - 1; // the tile in front, one level up
-    }
-    if (acc.count == 0) return;
-    mdb_m4_cell cell = cells[key];
-    m4_merge(cell, acc);
-    cells[key] = cell;
 }
 
 // The pieces of the MacaqueV streams bucket_values_by_pieces / bucket_tail_by_pieces take, as k_agg_bucket_pieces
@@ -237,31 +187,12 @@ static int m4_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, 
     const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
     const uint64_t n_slices = pair_slices + entry_slices;
     const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    void *p;
-    mdb_m4_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_m4_cell), &p)) return 1;
-        cells = static_cast<mdb_m4_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_m4_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(M4Partial), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    M4Partial *partials = pairs_scratch.take<M4Partial>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (records first: they are 64-byte aligned).
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(M4Partial)) + 256, &p)) return 1;
-    M4Partial *tree_values = static_cast<M4Partial *>(p);
-    unsigned long long *tree_keys = reinterpret_cast<unsigned long long *>(tree_values + tree_entries);
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_m4_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<M4FoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    M4Partial *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         // (slices of pairs first, then slices of the pieces' entries)
@@ -280,72 +211,21 @@ static int m4_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, 
                                ctx->stream, s, r, groups, piece_base, static_cast<const MvCursor *>(index->cursors),
                                (unsigned long long)n_pieces, entry_offsets, p0, p1, keys, partials);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        M4Tree tree = {};
-        tree.keys[0] = keys;
-        tree.values[0] = partials;
-        tree.n[0] = m;
-        tree.order = nullptr;
-        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-        }
-        // The tree's levels over this slice, then the fold.
-        tree.levels = 1;
-        uint64_t used = 0;
-        {
-            LaunchTimer timer(ctx, "k_m4_tree");
-            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-                unsigned long long *level_keys = tree_keys + used;
-                M4Partial *level_values = tree_values + used;
-                hipLaunchKernelGGL(k_m4_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                                   tree.levels - 1, level_keys, level_values);
-                tree.keys[tree.levels] = level_keys;
-                tree.values[tree.levels] = level_values;
-                tree.n[tree.levels] = up;
-                used += up + 1;
-                size = up;
-            }
-        }
-        {
-            LaunchTimer timer(ctx, "k_m4_fold");
-            hipLaunchKernelGGL(k_m4_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-        }
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_m4_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_m4_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int m4_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                 uint32_t n_inputs, const mdb_bucket_request *request, uint64_t n_cells, mdb_m4_cell *inout) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (an upload the library holds, as mdb_agg_buckets_list: the batch gets the cursor index a resident batch gets)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = m4_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, false)) return 1;
+    return m4_run(ctx, list.segments(), list.groups(), request, n_cells, nullptr, inout);
 }
 
 } // namespace mdb

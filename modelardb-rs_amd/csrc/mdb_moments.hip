@@ -2,8 +2,9 @@
 // the count, the mean and m2 = the sum of (v - mean)^2 - no point materialised.
 //
 // What the reference answers with GridExec -> AggregateExec(stddev / stddev_pop / var_samp / var_pop): its model-based
-// rule rewrites only count / min / max / sum / avg. The structure is that of mdb_m4.hip, whose span, scan, key check
-// and sort are shared (mdb_buckets.hpp); the partial is the 24-byte cell itself:
+// rule rewrites only count / min / max / sum / avg. The structure is that of mdb_m4.hip: the span, scan, key check
+// and sort are shared (mdb_buckets.hpp), the reduction tree and the fold are the one template of every per-bucket
+// operator (mdb_bucket_fold.hpp, with MomentsFoldOps of mdb_moments.hpp); the partial is the 24-byte cell itself:
 //
 //   k_agg_bucket_span   (shared) the buckets each segment reaches, its group id checked; a scan makes pair offsets.
 //   then per slice of at most MDB_AGG_BUCKET_SLICE_PAIRS pairs, slices folded one after the other:
@@ -15,8 +16,8 @@
 //   k_moments_pieces    1 lane / piece of 64 values, one entry {key, cell} per bucket the piece reaches; the entries
 //                       are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check  (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_moments_tree      runs of equal keys reduced through a fixed tree of 64-entry tiles.
-//   k_moments_fold      1 lane / pair: the lane of a run's last pair folds the run and merges it into the cell. No two
+//   k_moments_tree      (k_bucket_tree<MomentsFoldOps>) runs of equal keys reduced through a fixed tree of 64-entry tiles.
+//   k_moments_fold      (k_bucket_fold<MomentsFoldOps>) 1 lane / pair: the lane of a run's last pair folds the run and merges it into the cell. No two
 //                       lanes write one cell, no atomics on cells.
 // Every run of points is summed around its first value (mdb_moments.hpp) and runs meet only in moments_merge, in an
 // order fixed by the input, the request and the slice size: two runs of a call agree bit for bit, and a different
@@ -27,17 +28,8 @@
 #include "mdb_scan.hpp"
 
 #include <algorithm>
-#include <vector>
 
 namespace mdb {
-
-struct MomentsTree { // level 0 is the slice's pairs (keys, cells, and the sort's pair numbers); 1.. are the tree's
-    const unsigned long long *keys[BUCKET_MAX_LEVELS];
-    const mdb_moments_cell *values[BUCKET_MAX_LEVELS];
-    uint64_t n[BUCKET_MAX_LEVELS];
-    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
-    int levels;
-};
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_moments_partials(DevSegments s, const uint32_t *__restrict__ groups,
                                                                 BucketRequest r,
@@ -79,60 +71,6 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_moments_partials(DevSegments
         }
     }
     if (error) atomicOr(error_out, error);
-}
-
-__device__ __forceinline__ mdb_moments_cell moments_value(const MomentsTree &tree, int level, uint64_t t) {
-    return tree.values[level][level == 0 && tree.order ? tree.order[t] : t];
-}
-
-// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the fold of the run ending it.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_moments_tree(MomentsTree tree, int level,
-                                                            unsigned long long *__restrict__ keys_out,
-                                                            mdb_moments_cell *__restrict__ values_out) {
-    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[level];
-    const uint64_t first = u * BUCKET_TILE;
-    if (first >= n) return;
-    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
-    const unsigned long long *keys = tree.keys[level];
-    const unsigned long long key = keys[last];
-    mdb_moments_cell acc = moments_value(tree, level, last);
-    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) moments_merge(acc, moments_value(tree, level, t - 1));
-    keys_out[u] = key;
-    values_out[u] = acc;
-}
-
-// The lane of the last pair of each run of equal keys folds the run and merges it into its cell; a run without points
-// leaves the cell alone.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_moments_fold(MomentsTree tree, mdb_moments_cell *__restrict__ cells) {
-    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[0];
-    if (j >= n) return;
-    const unsigned long long key = tree.keys[0][j];
-    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
-    mdb_moments_cell acc = moments_empty();
-    uint64_t index = j;
-    for (int level = 0; level < tree.levels; level++) {
-        const uint64_t first = index - index % BUCKET_TILE;
-        const unsigned long long *keys = tree.keys[level];
-        uint64_t t = index;
-        bool whole = true; // every entry from `first` to `index` belongs to the run
-        while (true) {
-            if (keys[t] != key) {
-                whole = false;
-                break;
-            }
-            moments_merge(acc, moments_value(tree, level, t));
-            if (t == first) break;
-            t--;
-        }
-        if (!whole || first == 0) break;
-        index = first / BUCKET_TILE - 1; // the tile in front, one level up
-    }
-    if (acc.count == 0) return;
-    mdb_moments_cell cell = cells[key];
-    moments_merge(cell, acc);
-    cells[key] = cell;
 }
 
 // The pieces of the MacaqueV streams bucket_values_by_pieces / bucket_tail_by_pieces take, as k_agg_bucket_pieces
@@ -204,55 +142,6 @@ __global__ __launch_bounds__(MDB_WAVE) void k_moments_pieces(DevSegments s, Buck
     if (to_decode > 0) flush(); // (bucket == b_last)
 }
 
-int moments_tree_reserve(mdb_ctx *ctx, uint64_t cap, MomentsTreeScratch *out) {
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries (cells, then keys: both 8-byte aligned).
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    void *p;
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_moments_cell)) + 256, &p)) return 1;
-    out->values = static_cast<mdb_moments_cell *>(p);
-    out->keys = reinterpret_cast<unsigned long long *>(out->values + tree_entries);
-    return 0;
-}
-
-int moments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_moments_cell *partials, uint64_t m, bool unsorted,
-                       unsigned int key_bits, const MomentsTreeScratch &scratch, mdb_moments_cell *cells) {
-    MomentsTree tree = {};
-    tree.keys[0] = keys;
-    tree.values[0] = partials;
-    tree.n[0] = m;
-    tree.order = nullptr;
-    if (unsorted) { // keys out of order: a stable sort by key, pair numbers alongside
-        if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-    }
-    // The tree's levels over this slice, then the fold.
-    tree.levels = 1;
-    uint64_t used = 0;
-    {
-        LaunchTimer timer(ctx, "k_moments_tree");
-        for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-            const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-            unsigned long long *level_keys = scratch.keys + used;
-            mdb_moments_cell *level_values = scratch.values + used;
-            hipLaunchKernelGGL(k_moments_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                               tree.levels - 1, level_keys, level_values);
-            tree.keys[tree.levels] = level_keys;
-            tree.values[tree.levels] = level_values;
-            tree.n[tree.levels] = up;
-            used += up + 1;
-            size = up;
-        }
-    }
-    {
-        LaunchTimer timer(ctx, "k_moments_fold");
-        hipLaunchKernelGGL(k_moments_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-    }
-    return 0;
-}
-
 // The buckets of the device batch `in` (groups: a device array or nullptr) merged into a device array of n_cells
 // cells. `host_cells` (host forms): the caller's array, which is uploaded, merged into and downloaded instead; either
 // way nothing of the caller's is written unless the whole call succeeds.
@@ -282,24 +171,12 @@ static int moments_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *gro
     const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
     const uint64_t n_slices = pair_slices + entry_slices;
     const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    void *p;
-    mdb_moments_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_moments_cell), &p)) return 1;
-        cells = static_cast<mdb_moments_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_moments_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(mdb_moments_cell), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    mdb_moments_cell *partials = pairs_scratch.take<mdb_moments_cell>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    MomentsTreeScratch tree_scratch;
-    if (moments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_moments_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<MomentsFoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    mdb_moments_cell *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         // (slices of pairs first, then slices of the pieces' entries)
@@ -318,43 +195,21 @@ static int moments_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *gro
                                ctx->stream, s, r, groups, piece_base, static_cast<const MvCursor *>(index->cursors),
                                (unsigned long long)n_pieces, entry_offsets, p0, p1, keys, partials);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        if (moments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_moments_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_moments_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int moments_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                 uint32_t n_inputs, const mdb_bucket_request *request, uint64_t n_cells, mdb_moments_cell *inout) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (an upload the library holds, as mdb_agg_buckets_list: the batch gets the cursor index a resident batch gets)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = moments_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, false)) return 1;
+    return moments_run(ctx, list.segments(), list.groups(), request, n_cells, nullptr, inout);
 }
 
 } // namespace mdb

@@ -17,7 +17,7 @@
 #include <cstring>
 
 #if defined(__HIPCC__)
-#include "mdb_buckets.hpp"
+#include "mdb_bucket_fold.hpp"
 #define MDB_MOMENTS_FN __host__ __device__ __forceinline__
 #else
 #include "mdb_host_side.hpp"
@@ -95,19 +95,17 @@ int moments_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint
 
 namespace mdb {
 
-// mdb_moments.hip, for the operators whose partials are moments cells (mdb_binned.hip too). The upper levels of the
-// reduction tree over slices of at most `cap` entries (SCRATCH_BUCKET_TREE), and one slice folded: the m entries
-// {keys[j], partials[j]} - `unsorted`: what bucket_keys_check found, the keys are then sorted by key_bits bits, stably -
-// reduced by k_moments_tree and merged into cells[key] by k_moments_fold, enqueued on the context's stream.
-struct MomentsTreeScratch {
-    mdb_moments_cell *values;
-    unsigned long long *keys;
-};
-int moments_tree_reserve(mdb_ctx *ctx, uint64_t cap, MomentsTreeScratch *out);
-int moments_fold_slice(mdb_ctx *ctx, unsigned long long *keys, const mdb_moments_cell *partials, uint64_t m, bool unsorted,
-                       unsigned int key_bits, const MomentsTreeScratch &scratch, mdb_moments_cell *cells);
-
 __device__ __forceinline__ mdb_moments_cell moments_empty() { return mdb_moments_cell{0, 0.0, 0.0}; }
+
+// What the tree and fold (mdb_bucket_fold.hpp) need to know of a moments cell: for mdb_moments.hip and for
+// mdb_binned.hip, whose partials are moments cells too (each instantiates BucketFold<MomentsFoldOps> itself).
+struct MomentsFoldOps : FoldOps<mdb_moments_cell> {
+    static constexpr const char *tree_name = "k_moments_tree", *fold_name = "k_moments_fold";
+    __device__ __forceinline__ static mdb_moments_cell empty() { return moments_empty(); }
+    __device__ __forceinline__ static void merge(mdb_moments_cell &into, const mdb_moments_cell &from) { moments_merge(into, from); }
+    __device__ __forceinline__ static bool is_empty(const mdb_moments_cell &acc) { return acc.count == 0; }
+    __device__ __forceinline__ void apply(mdb_moments_cell &cell, const mdb_moments_cell &acc) const { moments_merge(cell, acc); }
+};
 
 // The model points [a, b] of a PMC-Mean or Swing segment with regular timestamps, merged into `acc`. PMC-Mean: n equal
 // values, exact in O(1). Swing: (float)(slope * t + intercept) point by point in registers - the rebuilt points are f32

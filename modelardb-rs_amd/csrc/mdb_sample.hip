@@ -16,26 +16,30 @@
 //   k_sample_walk_pairs   1 lane / segment with pairs in the slice and anything left: MacaqueV values, irregular
 //                         timestamps, a residual tail, the link - one walk of the rows, ADDED into the lane's own slots.
 //   k_agg_bucket_check    (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_sample_tree, k_sample_fold  the bucket tree and fold for a {u64, f64} partial merged with sample_cell_add: runs
+//   k_sample_tree, k_sample_fold  the one tree and fold of every per-bucket operator (mdb_bucket_fold.hpp:
+//                         k_bucket_tree / k_bucket_fold<SampleFoldOps>) for a {u64, f64} partial merged with
+//                         sample_cell_add: runs
 //                         of equal keys reduced through the fixed tree of 64-entry tiles and merged into the cells by
 //                         the lane of each run's last pair. No two lanes write one cell, no float atomics, every
 //                         addition's order fixed by the pair order.
 //
 // Scratch: 16 B per pair (the cell) and the 8-byte key, written and read back; 8 B per segment of heads.
+#include "mdb_bucket_fold.hpp"
 #include "mdb_sample.hpp"
 #include "mdb_scan.hpp"
 
 #include <algorithm>
-#include <vector>
 
 namespace mdb {
 
-struct SampleTree { // level 0 is the slice's pairs (keys, cells, and the sort's pair numbers); 1.. are the tree's
-    const unsigned long long *keys[BUCKET_MAX_LEVELS];
-    const mdb_sample_cell *values[BUCKET_MAX_LEVELS];
-    uint64_t n[BUCKET_MAX_LEVELS];
-    const uint32_t *order; // (level 0 in key order: values[0][order[j]]; nullptr: pair order)
-    int levels;
+// What the tree and fold (mdb_bucket_fold.hpp) need to know of the {u64, f64} cell: merged with sample_cell_add, and a
+// run without a contribution leaves its cell alone.
+struct SampleFoldOps : FoldOps<mdb_sample_cell> {
+    static constexpr const char *tree_name = "k_sample_tree", *fold_name = "k_sample_fold";
+    __device__ __forceinline__ static mdb_sample_cell empty() { return mdb_sample_cell{0, 0.0}; }
+    __device__ __forceinline__ static void merge(mdb_sample_cell &into, const mdb_sample_cell &from) { sample_cell_add(into, from); }
+    __device__ __forceinline__ static bool is_empty(const mdb_sample_cell &acc) { return acc.count == 0; }
+    __device__ __forceinline__ void apply(mdb_sample_cell &cell, const mdb_sample_cell &acc) const { sample_cell_add(cell, acc); }
 };
 
 __global__ __launch_bounds__(BUCKET_THREADS) void k_sample_span(DevSegments s, const uint32_t *__restrict__ groups,
@@ -105,58 +109,6 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_sample_walk_pairs(DevSegment
     if (error) atomicOr(error_out, error);
 }
 
-__device__ __forceinline__ mdb_sample_cell sample_tree_value(const SampleTree &tree, int level, uint64_t t) {
-    return tree.values[level][level == 0 && tree.order ? tree.order[t] : t];
-}
-
-// Level `level` + 1 from `level`: per tile of BUCKET_TILE entries its last key and the sum of the run ending it.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_sample_tree(SampleTree tree, int level,
-                                                                unsigned long long *__restrict__ keys_out,
-                                                                mdb_sample_cell *__restrict__ values_out) {
-    const uint64_t u = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[level];
-    const uint64_t first = u * BUCKET_TILE;
-    if (first >= n) return;
-    const uint64_t last = min(first + BUCKET_TILE, n) - 1;
-    const unsigned long long *keys = tree.keys[level];
-    const unsigned long long key = keys[last];
-    mdb_sample_cell acc = sample_tree_value(tree, level, last);
-    for (uint64_t t = last; t > first && keys[t - 1] == key; t--) sample_cell_add(acc, sample_tree_value(tree, level, t - 1));
-    keys_out[u] = key;
-    values_out[u] = acc;
-}
-
-// The lane of the last pair of each run of equal keys sums the run (its tile, then one tile's entry per level up) and
-// merges it into its cell; a run without a contribution leaves the cell alone.
-__global__ __launch_bounds__(BUCKET_THREADS) void k_sample_fold(SampleTree tree, mdb_sample_cell *__restrict__ cells) {
-    const uint64_t j = (uint64_t)blockIdx.x * BUCKET_THREADS + threadIdx.x;
-    const uint64_t n = tree.n[0];
-    if (j >= n) return;
-    const unsigned long long key = tree.keys[0][j];
-    if (j + 1 < n && tree.keys[0][j + 1] == key) return;
-    mdb_sample_cell acc = {0, 0.0};
-    uint64_t index = j;
-    for (int level = 0; level < tree.levels; level++) {
-        const uint64_t first = index - index % BUCKET_TILE;
-        const unsigned long long *keys = tree.keys[level];
-        bool whole = true; // every entry from `first` to `index` belongs to the run
-        for (uint64_t t = index;; t--) { // (at most BUCKET_TILE entries)
-            if (keys[t] != key) {
-                whole = false;
-                break;
-            }
-            sample_cell_add(acc, sample_tree_value(tree, level, t));
-            if (t == first) break;
-        }
-        if (!whole || first == 0) break;
-        index = first / BUCKET_TILE - 1; // the tile in front, one level up
-    }
-    if (acc.count == 0) return;
-    mdb_sample_cell cell = cells[key];
-    sample_cell_add(cell, acc);
-    cells[key] = cell;
-}
-
 static void sample_span_launch(mdb_ctx *ctx, const DevSegments &s, const uint32_t *groups, const BucketRequest &,
                                unsigned long long *counts, unsigned int *error, const void *arg) {
     hipLaunchKernelGGL(k_sample_span, dim3(blocks_for(s.n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups,
@@ -188,30 +140,12 @@ static int sample_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *grou
     void *p;
     if (scratch_reserve(ctx, SCRATCH_INTEGRAL_HEADS, n * sizeof(IntegralHead), &p)) return 1;
     IntegralHead *heads = static_cast<IntegralHead *>(p);
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    mdb_sample_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_sample_cell), &p)) return 1;
-        cells = static_cast<mdb_sample_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_sample_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(mdb_sample_cell), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    mdb_sample_cell *partials = pairs_scratch.take<mdb_sample_cell>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    // The tree's upper levels: ceil(n / 64) + ceil(n / 64^2) + ... entries.
-    uint64_t tree_entries = 0;
-    for (uint64_t m = cap; m > BUCKET_TILE;) {
-        m = (m + BUCKET_TILE - 1) / BUCKET_TILE;
-        tree_entries += m + 1;
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_TREE, tree_entries * (8 + sizeof(mdb_sample_cell)) + 256, &p)) return 1;
-    unsigned long long *tree_keys = static_cast<unsigned long long *>(p);
-    mdb_sample_cell *tree_values = reinterpret_cast<mdb_sample_cell *>(tree_keys + tree_entries);
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_sample_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<SampleFoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    mdb_sample_cell *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     // (the words are zero: bucket_span_pairs left them so; the heads' errors are read back with the first slice's)
     if (request->method != MDB_SAMPLE_EXACT) integral_heads_launch(ctx, s, groups, offsets, heads, words);
@@ -228,71 +162,21 @@ static int sample_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *grou
             hipLaunchKernelGGL(k_sample_walk_pairs, dim3(blocks_for(n)), dim3(BUCKET_THREADS), 0, ctx->stream, s, groups, q,
                                offsets, p0, p1, heads, partials, words);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        SampleTree tree = {};
-        tree.keys[0] = keys;
-        tree.values[0] = partials;
-        tree.n[0] = m;
-        tree.order = nullptr;
-        if (read_back[1]) { // keys out of order: a stable sort by key, pair numbers alongside
-            if (bucket_keys_sort(ctx, keys, m, key_bits, &tree.keys[0], &tree.order)) return 1;
-        }
-        tree.levels = 1;
-        uint64_t used = 0;
-        {
-            LaunchTimer timer(ctx, "k_sample_tree");
-            for (uint64_t size = m; size > BUCKET_TILE; tree.levels++) {
-                const uint64_t up = (size + BUCKET_TILE - 1) / BUCKET_TILE;
-                unsigned long long *level_keys = tree_keys + used;
-                mdb_sample_cell *level_values = tree_values + used;
-                hipLaunchKernelGGL(k_sample_tree, dim3(blocks_for(up)), dim3(BUCKET_THREADS), 0, ctx->stream, tree,
-                                   tree.levels - 1, level_keys, level_values);
-                tree.keys[tree.levels] = level_keys;
-                tree.values[tree.levels] = level_values;
-                tree.n[tree.levels] = up;
-                used += up + 1;
-                size = up;
-            }
-        }
-        {
-            LaunchTimer timer(ctx, "k_sample_fold");
-            hipLaunchKernelGGL(k_sample_fold, dim3(blocks_for(m)), dim3(BUCKET_THREADS), 0, ctx->stream, tree, cells);
-        }
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_sample_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_sample_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int sample_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                     uint32_t n_inputs, const mdb_sample_request *request, uint64_t n_cells, mdb_sample_cell *inout) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (an upload the library holds, as mdb_integral_buckets_list: the host and device forms run the same kernels)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = sample_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, false)) return 1;
+    return sample_run(ctx, list.segments(), list.groups(), request, n_cells, nullptr, inout);
 }
 
 } // namespace mdb

@@ -142,22 +142,10 @@ int transit_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *groups, co
 int transit_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                      uint32_t n_inputs, const mdb_transit_request *request, const std::vector<int32_t> &edge_keys,
                      uint64_t n_rows, uint64_t *counts) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (into the context's upload scratch, as mdb_dwell_buckets_list: the host and device forms run the same kernels)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, true, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = transit_run(ctx, &dev->seg, groups, request, edge_keys, n_rows, nullptr, counts);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, true)) return 1;
+    return transit_run(ctx, list.segments(), list.groups(), request, edge_keys, n_rows, nullptr, counts);
 }
 
 } // namespace mdb

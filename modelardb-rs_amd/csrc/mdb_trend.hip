@@ -4,8 +4,9 @@
 // What the reference answers with GridExec -> AggregateExec(regr_slope(field, ts) / regr_r2 / corr / covar_*) over
 // every rebuilt point. mdb_comoments_buckets* cannot stand in: its y is a second field column, and a timestamp does
 // not fit an f32. Here the time side needs no data at all. The structure is that of mdb_moments.hip with a 48-byte
-// partial; the span, scan, key check and sort are shared (mdb_buckets.hpp), and so are the tree and the fold of
-// mdb_comoments.hip (comoments_tree_reserve / comoments_fold_slice):
+// partial; the span, scan, key check and sort are shared (mdb_buckets.hpp), and the tree and the fold are the one
+// template of every per-bucket operator (mdb_bucket_fold.hpp), instantiated here with mdb_comoments.hpp's
+// ComomentsFoldOps - under the names mdb_comoments.hip's launches have:
 //
 //   k_agg_bucket_span   (shared) the buckets each segment reaches, its group id checked; a scan makes pair offsets.
 //   then per slice of at most MDB_AGG_BUCKET_SLICE_PAIRS pairs, slices folded one after the other:
@@ -18,7 +19,8 @@
 //   k_trend_pieces      1 lane / piece of 64 values, one entry {key, cell} per bucket the piece reaches; the entries
 //                       are reduced and folded like the pairs, in slices behind them.
 //   k_agg_bucket_check  (shared) keys non-decreasing? If not, a stable radix sort by key.
-//   k_comoments_tree, k_comoments_fold  (mdb_comoments.hip) runs of equal keys reduced and merged into the cells.
+//   k_comoments_tree, k_comoments_fold  (k_bucket_tree / k_bucket_fold<ComomentsFoldOps>) runs of equal keys reduced
+//                       and merged into the cells.
 // Every run is summed around its first pair (mdb_trend.hpp) and runs meet only in comoments_merge, in an order fixed by
 // the input, the request and the slice size: two runs of a call agree bit for bit, and a different order of merges
 // moves the five doubles by rounding only. No y column, no strided read, no scratch beyond the pairs.
@@ -28,7 +30,6 @@
 #include "mdb_scan.hpp"
 
 #include <algorithm>
-#include <vector>
 
 namespace mdb {
 
@@ -177,24 +178,12 @@ static int trend_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group
     const uint64_t pair_slices = (total + slice - 1) / slice, entry_slices = (entries + slice - 1) / slice;
     const uint64_t n_slices = pair_slices + entry_slices;
     const uint64_t cap = std::min<uint64_t>(slice, std::max<uint64_t>(total, entries));
-    // Where the slices are folded: the caller's device array when nothing can fail after the first fold (one slice),
-    // a working copy otherwise.
-    void *p;
-    mdb_comoments_cell *cells = dev_cells;
-    if (host_cells || n_slices > 1) {
-        if (scratch_reserve(ctx, SCRATCH_BUCKET_CELLS, n_cells * sizeof(mdb_comoments_cell), &p)) return 1;
-        cells = static_cast<mdb_comoments_cell *>(p);
-        MDB_HIP_CHECK(hipMemcpyAsync(cells, host_cells ? host_cells : dev_cells, n_cells * sizeof(mdb_comoments_cell),
-                                     host_cells ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (scratch_reserve(ctx, SCRATCH_BUCKET_PAIRS, align_up(cap * sizeof(mdb_comoments_cell), 256) + cap * 8, &p)) return 1;
-    Carver pairs_scratch(p);
-    mdb_comoments_cell *partials = pairs_scratch.take<mdb_comoments_cell>(cap);
-    unsigned long long *keys = pairs_scratch.take<unsigned long long>(cap);
-    ComomentsTreeScratch tree_scratch;
-    if (comoments_tree_reserve(ctx, cap, &tree_scratch)) return 1;
-    const unsigned long long max_key = (unsigned long long)(n_cells - 1);
-    const unsigned int key_bits = max_key == 0 ? 1u : 64u - (unsigned int)__builtin_clzll(max_key);
+    BucketCells<mdb_comoments_cell> cells;
+    if (cells.stage(ctx, n_cells, dev_cells, host_cells, n_slices)) return 1;
+    BucketFold<ComomentsFoldOps> fold;
+    if (fold.reserve(ctx, cap, n_cells)) return 1;
+    mdb_comoments_cell *partials = fold.partials();
+    unsigned long long *keys = fold.keys();
 
     for (uint64_t k = 0; k < n_slices; k++) {
         // (slices of pairs first, then slices of the pieces' entries)
@@ -213,43 +202,21 @@ static int trend_run(mdb_ctx *ctx, const mdb_segments *in, const uint32_t *group
                                ctx->stream, s, r, groups, piece_base, static_cast<const MvCursor *>(index->cursors),
                                (unsigned long long)n_pieces, entry_offsets, p0, p1, keys, partials);
         }
-        bucket_keys_check(ctx, keys, m, words + 1);
-        unsigned int read_back[2] = {0, 0};
-        MDB_HIP_CHECK(hipMemcpyAsync(read_back, words, 8, hipMemcpyDeviceToHost, ctx->stream));
-        MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        MDB_HIP_CHECK(hipGetLastError());
-        if (read_back[0]) return fail(describe_error(read_back[0]));
-
-        if (comoments_fold_slice(ctx, keys, partials, m, read_back[1] != 0, key_bits, tree_scratch, cells)) return 1;
+        unsigned int error = 0;
+        bool unsorted = false;
+        if (bucket_slice_check(ctx, keys, m, words, &error, &unsorted)) return 1;
+        if (error) return fail(describe_error(error));
+        if (fold.fold_slice(ctx, m, unsorted, cells.cells())) return 1;
     }
-    // (every slice has been found free of errors: the caller's cells are written now, and only now)
-    if (host_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(host_cells, cells, n_cells * sizeof(mdb_comoments_cell), hipMemcpyDeviceToHost, ctx->stream));
-    else if (cells != dev_cells)
-        MDB_HIP_CHECK(hipMemcpyAsync(dev_cells, cells, n_cells * sizeof(mdb_comoments_cell), hipMemcpyDeviceToDevice, ctx->stream));
-    MDB_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    MDB_HIP_CHECK(hipGetLastError());
-    return 0;
+    return cells.commit();
 }
 
 int trend_list_run(mdb_ctx *ctx, const mdb_segments *const *inputs, const uint32_t *const *group_of_segment,
                    uint32_t n_inputs, const mdb_bucket_request *request, uint64_t n_cells, mdb_comoments_cell *inout) {
-    std::vector<uint64_t> rows(n_inputs);
-    uint64_t n = 0;
-    for (uint32_t k = 0; k < n_inputs; k++) {
-        rows[k] = inputs[k]->n;
-        n += rows[k];
-    }
-    mdb::CallGuard lock(ctx);
-    MDB_HIP_CHECK(hipSetDevice(ctx->device));
     // (an upload the library holds, as mdb_moments_buckets_list: the batch gets the cursor index a resident batch gets)
-    mdb_segments_owned *dev = nullptr;
-    if (upload_segment_list_locked(ctx, inputs, n_inputs, false, &dev)) return 1;
-    const uint32_t *groups = nullptr;
-    int rc = upload_groups(ctx, group_of_segment, rows.data(), n_inputs, n, &groups);
-    if (!rc) rc = trend_run(ctx, &dev->seg, groups, request, n_cells, nullptr, inout);
-    mdb_segments_free(dev);
-    return rc;
+    UploadedSegments list(ctx);
+    if (list.upload(inputs, n_inputs, group_of_segment, false)) return 1;
+    return trend_run(ctx, list.segments(), list.groups(), request, n_cells, nullptr, inout);
 }
 
 } // namespace mdb
