@@ -575,6 +575,80 @@ int mdb_comoments_moments(const mdb_comoments_cell *cells, uint64_t n, uint32_t 
 /* Host arithmetic, no context, no GPU: out[j] = the MDB_COMOMENTS_* statistic `kind` of cells[j] (NaN as listed). */
 int mdb_comoments_finish(const mdb_comoments_cell *cells, uint64_t n, uint32_t kind, double *out);
 
+/* Extension: DERIVED FIELDS of two fields - the generated column z = f(x, y) and, per date_bin bucket and group, its
+ * count, mean, m2, MIN and MAX:
+ *   power = voltage * current, dT = outlet - inlet, efficiency = output / input, |forecast - actual| (MAE, largest error)
+ * A generated field FIELD AS (column_one + column_two) is answered by the reference with GridExec per field ->
+ * SortedJoinExec -> GeneratedAsExec -> AggregateExec (crates/modelardb_storage/src/query/generated_as_exec.rs; the
+ * fields are zipped by row position, query/sorted_join_exec.rs:278-310): every point of both fields is rebuilt on the
+ * host. Here both fields are rebuilt values-only into two scratch columns that live in HBM only, and the reduction
+ * runs over ROWS, not over segments: a derived field needs every row of both fields whatever the model type.
+ *   expr: mdb_derived_expr (mdb_format.h) - LINEAR, PRODUCT or RATIO with finite a, b, c and the optional ABS flag;
+ *     binary32 operations in the written order, nothing fused, denormals kept, the correctly rounded division.
+ *   x, y: two field columns of the same series with the same timestamps, each cut into segments in its own way (the
+ *     alignment rule of the row masks); y may be the same batch as x.
+ *   Which points: the rows of mdb_grid_batch_range(x, t_lo, t_hi) and of mdb_grid_batch_range(y, t_lo, t_hi), in
+ *     order; row r of one is paired with row r of the other. Only the row COUNT under [t_lo, t_hi] is checked; a
+ *     mismatch fails before anything is written, with a message that names both counts.
+ *   mdb_derived_values*: values[r] = f(x[r], y[r]) for every row, timestamps[r] (or NULL) x's timestamp; *rows_out the
+ *     row count. capacity smaller than the row count is an error that names the count. _dev: device batches and device
+ *     outputs; values needs 4-byte alignment only, timestamps 16-byte alignment. The other form takes host batches and
+ *     host outputs.
+ *   mdb_derived_buckets*: request is mdb_bucket_request, unchanged; which_mask must be 0. inout: row-major
+ *     [n_groups][n_buckets] cells (mdb_derived_cell, mdb_format.h); a fresh cell is all-zero bytes. A pair takes the
+ *     bucket of its x-side timestamp and the group of its x-side segment, and is counted exactly where mdb_agg_buckets
+ *     counts the x point for the same request: count equals that COUNT, always.
+ *   How: per (x segment, bucket) pair the interval of rows it holds - O(1) on regular timestamps for every model type,
+ *     one pass over the timestamps of a segment otherwise. An interval of at most MDB_DERIVED_SHORT_ROWS rows is reduced
+ *     by one lane; a longer one is cut at the multiples of MDB_DERIVED_CHUNK_ROWS in absolute row numbers and one wave
+ *     reduces each chunk with 16-byte loads of both columns. A run (an interval, or a lane's share of a chunk) is
+ *     summed around its first z as mdb_moments_buckets sums a run; runs meet only through the merge rule.
+ *   Merge rule, the same in mdb_derived_merge_n and in every kernel: count, mean and m2 as mdb_moments_merge_n; min and
+ *     max by mdb_agg_buckets' rule for MIN and MAX (mdb_format.h: a NaN is skipped, -0.0 == +0.0 and the first one
+ *     met stays - the sign of a zero extreme is the only thing about min and max that follows the order of merges); an
+ *     empty side gives the other side's bytes. A cell of equal z has m2 == 0.0 and mean == z exactly, in any order of
+ *     merges. A cell that receives no pair keeps every byte it had.
+ *   Non-finite z: count is exact, min and max skip NaNs, and neither mean nor m2 is finite; nothing more is promised.
+ *   Determinism: for the same input, request, expression and form two runs agree bit for bit, and so do the host, dev
+ *     and list forms; no float atomics, no atomics on cells. MDB_AGG_BUCKET_SLICE_PAIRS, the order of the segments and
+ *     cutting a batch into calls move mean and m2 by rounding only and never count, min or max.
+ *   Scratch: the two columns take 8 B per row under [t_lo, t_hi]. Under mdb_set_scratch_limit columns larger than the
+ *     limit are refused with a message that states the bytes needed: cut the batch by series, the cells merge.
+ *   Errors (mdb_last_error set, inout and the outputs untouched - with one exception, that of mdb_grid_batch_range_dev:
+ *     mdb_derived_values* lets the range grid of x write timestamps, and values where it is 16-byte aligned, in place,
+ *     so a bit stream of x that turns out malformed only while it is decoded fails the call after rows have been
+ *     written; everything the row plans find, and every error of y, whose grid runs first and into scratch, comes
+ *     before the first store): those of mdb_moments_buckets*, a NULL y or expr, an
+ *     unknown op or flag bit, a NaN or infinite a, b or c, the row-count mismatch, the columns refused, a capacity too
+ *     small, a malformed segment in x or y. An empty batch, n_buckets == 0 or an empty range succeeds and changes
+ *     nothing (*rows_out = 0). */
+#define MDB_DERIVED_SHORT_ROWS 64u    /* an interval of at most this many rows: one lane */
+#define MDB_DERIVED_CHUNK_ROWS 1024u  /* a longer one: one wave per chunk of this many rows */
+int mdb_derived_values_dev(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, const mdb_derived_expr *expr,
+                           int64_t t_lo, int64_t t_hi, int64_t *timestamps, float *values, uint64_t capacity,
+                           uint64_t *rows_out);
+/* Host batches, host outputs. */
+int mdb_derived_values(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, const mdb_derived_expr *expr,
+                       int64_t t_lo, int64_t t_hi, int64_t *timestamps, float *values, uint64_t capacity,
+                       uint64_t *rows_out);
+int mdb_derived_buckets(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y, const uint32_t *group_of_segment_x,
+                        const mdb_bucket_request *request, const mdb_derived_expr *expr, mdb_derived_cell *inout);
+/* All device pointers: both batches, group_of_segment_x and inout are in HBM (expr is a host pointer). */
+int mdb_derived_buckets_dev(mdb_ctx *ctx, const mdb_segments *x, const mdb_segments *y,
+                            const uint32_t *group_of_segment_x, const mdb_bucket_request *request,
+                            const mdb_derived_expr *expr, mdb_derived_cell *inout);
+/* Several host batches per field (rows in the order of each list) folded as one batch per field; group_of_segment_x:
+ * one array per batch of xs, or NULL. */
+int mdb_derived_buckets_list(mdb_ctx *ctx, const mdb_segments *const *xs, uint32_t n_x, const mdb_segments *const *ys,
+                             uint32_t n_y, const uint32_t *const *group_of_segment_x,
+                             const mdb_bucket_request *request, const mdb_derived_expr *expr, mdb_derived_cell *inout);
+/* Host arithmetic, no context, no GPU: z[j] = f(x[j], y[j]) for j < n, by the evaluator the kernels use. */
+int mdb_derived_apply(const mdb_derived_expr *expr, const float *x, const float *y, uint64_t n, float *z);
+/* Host arithmetic, no context, no GPU: into[j] merged with from[j] by the merge rule, for j < n. */
+int mdb_derived_merge_n(mdb_derived_cell *into, const mdb_derived_cell *from, uint64_t n);
+/* Host arithmetic, no context, no GPU: out[j] = (count, mean, m2) of cells[j]: what mdb_moments_variance takes. */
+int mdb_derived_stats(const mdb_derived_cell *cells, uint64_t n, mdb_moments_cell *out);
+
 /* Extension: value histograms and exact quantiles PER BUCKET of date_bin(width, ts, origin) and group -
  *   SELECT date_bin(...), approx_percentile_cont(field, 0.95) ... GROUP BY 1 / median(field) per bucket / a heat map
  *   (time bucket x value cell),

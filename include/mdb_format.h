@@ -230,6 +230,36 @@ typedef struct mdb_comoments_cell {
     double  c_xy;         /* sum (x - mean_x) * (y - mean_y) */
 } mdb_comoments_cell;      /* 48 bytes */
 
+/* The expression of mdb_derived_*: a generated field z = f(x, y) of two fields (FIELD AS (column_one + column_two)).
+ * Every operation is one IEEE-754 binary32 operation, rounded to nearest, in the written order; nothing is fused,
+ * denormals are kept (operands and results) and the division is the correctly rounded one. Zeros follow from the
+ * formula as written and are not special-cased: c = +0 turns a -0 sum into +0, c = -0 keeps it. a, b and c must be
+ * finite; an unknown op or flag bit is an error. */
+#define MDB_DERIVED_LINEAR  0u   /* z = ((a * x) + (b * y)) + c */
+#define MDB_DERIVED_PRODUCT 1u   /* z = (a * (x * y)) + c        (b is not read) */
+#define MDB_DERIVED_RATIO   2u   /* z = (a * (x / y)) + c        (b is not read) */
+#define MDB_DERIVED_ABS     1u   /* flag: z = |z| (sign bit cleared, also of a NaN) */
+typedef struct mdb_derived_expr {
+    uint32_t op;          /* MDB_DERIVED_LINEAR / _PRODUCT / _RATIO */
+    uint32_t flags;       /* 0 or MDB_DERIVED_ABS */
+    float    a, b, c;
+} mdb_derived_expr;        /* 20 bytes */
+
+/* One cell of mdb_derived_buckets*: the count, the mean and m2 = the sum of (z - mean)^2 of the generated values z of
+ * a bucket and group, and their extremes. A fresh cell is all-zero bytes. count == 0: the cell is empty and no other
+ * member is read or meaningful; all are written when its first values arrive.
+ * count, mean, m2: the rules of mdb_moments_cell. min, max: the rule of mdb_agg_buckets' MIN and MAX - a run starts
+ * at min = FLT_MAX, max = -FLT_MAX and takes a value by min = (z < min) ? z : min, max = (z > max) ? z : max, so a
+ * NaN is skipped (a cell of NaNs only keeps FLT_MAX / -FLT_MAX, and FLT_MAX stays the min of a cell of +inf only),
+ * and -0.0 and +0.0 compare equal: the one met first stays. */
+typedef struct mdb_derived_cell {
+    int64_t count;
+    double  mean;
+    double  m2;
+    float   min;
+    float   max;
+} mdb_derived_cell;        /* 32 bytes */
+
 /* One cell of mdb_integral_buckets*: the series of a bucket and group taken as a function of time. duration: the
  * microseconds of the bucket on which the function is defined (the clipped linked intervals, mdb.h), exact; integral:
  * the integral of the function over them, in value * microseconds. The time-weighted average is integral / duration
@@ -422,6 +452,18 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, mean_y) == 16);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_x) == 24);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, m2_y) == 32);
 MDB_LAYOUT_ASSERT(offsetof(mdb_comoments_cell, c_xy) == 40);
+MDB_LAYOUT_ASSERT(sizeof(mdb_derived_expr) == 20);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_expr, op) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_expr, flags) == 4);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_expr, a) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_expr, b) == 12);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_expr, c) == 16);
+MDB_LAYOUT_ASSERT(sizeof(mdb_derived_cell) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_cell, count) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_cell, mean) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_cell, m2) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_cell, min) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_derived_cell, max) == 28);
 MDB_LAYOUT_ASSERT(sizeof(mdb_integral_cell) == 16);
 MDB_LAYOUT_ASSERT(offsetof(mdb_integral_cell, integral) == 8);
 MDB_LAYOUT_ASSERT(sizeof(mdb_integral_request) == 64);

@@ -364,6 +364,38 @@ class ComomentsCellC(C.Structure):
     ]
 
 
+MDB_DERIVED_LINEAR = 0
+MDB_DERIVED_PRODUCT = 1
+MDB_DERIVED_RATIO = 2
+MDB_DERIVED_ABS = 1
+MDB_DERIVED_SHORT_ROWS = 64     # an interval of at most this many rows is reduced by one lane
+MDB_DERIVED_CHUNK_ROWS = 1024   # a longer one by one wave per chunk of this many rows
+
+
+class DerivedExprC(C.Structure):
+    """mdb_derived_expr: z = f(x, y) of mdb_derived_* - LINEAR ((a * x) + (b * y)) + c, PRODUCT (a * (x * y)) + c or
+    RATIO (a * (x / y)) + c, with the optional ABS flag."""
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("a", C.c_float),
+        ("b", C.c_float),
+        ("c", C.c_float),
+    ]
+
+
+class DerivedCellC(C.Structure):
+    """mdb_derived_cell: the count, mean, m2, min and max of the generated values z of one bucket and group
+    (mdb_derived_buckets*)."""
+    _fields_ = [
+        ("count", C.c_int64),
+        ("mean", C.c_double),
+        ("m2", C.c_double),
+        ("min", C.c_float),
+        ("max", C.c_float),
+    ]
+
+
 class HistRequestC(C.Structure):
     """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
     _fields_ = [
@@ -471,6 +503,21 @@ _HIP_SYMBOLS = {
     "mdb_comoments_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_comoments_moments": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "mdb_comoments_finish": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "mdb_derived_values_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.POINTER(DerivedExprC),
+                                         C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.POINTER(C.c_uint64)]),
+    "mdb_derived_values": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.POINTER(DerivedExprC),
+                                     C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "mdb_derived_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
+                                      C.POINTER(BucketRequestC), C.POINTER(DerivedExprC), C.c_void_p]),
+    "mdb_derived_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.POINTER(SegmentsC), C.c_void_p,
+                                          C.POINTER(BucketRequestC), C.POINTER(DerivedExprC), C.c_void_p]),
+    "mdb_derived_buckets_list": (C.c_int, [C.c_void_p, C.POINTER(C.POINTER(SegmentsC)), C.c_uint32,
+                                           C.POINTER(C.POINTER(SegmentsC)), C.c_uint32, C.POINTER(C.c_void_p),
+                                           C.POINTER(BucketRequestC), C.POINTER(DerivedExprC), C.c_void_p]),
+    "mdb_derived_apply": (C.c_int, [C.POINTER(DerivedExprC), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mdb_derived_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_derived_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "mdb_trend_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
                                     C.c_void_p]),
     "mdb_trend_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),

@@ -263,6 +263,68 @@ def comoments_finish(cells, kind):
     return out.reshape(cells.shape)
 
 
+# mdb_derived_cell as a numpy record: the cells of mdb_derived_buckets*, row-major [n_groups][n_buckets].
+DERIVED_CELL_DTYPE = np.dtype([("count", "<i8"), ("mean", "<f8"), ("m2", "<f8"), ("min", "<f4"), ("max", "<f4")])
+assert DERIVED_CELL_DTYPE.itemsize == C.sizeof(_abi.DerivedCellC) == 32
+
+# The operations of mdb_derived_expr (MDB_DERIVED_*): z = ((a * x) + (b * y)) + c, (a * (x * y)) + c, (a * (x / y)) + c.
+DERIVED_OPS = {"linear": 0, "product": 1, "ratio": 2}
+
+
+def derived_expr(op, a=1.0, b=1.0, c=0.0, absolute=False):
+    """An mdb_derived_expr: `op` a name of DERIVED_OPS or its number; `absolute` sets MDB_DERIVED_ABS. An expression
+    made elsewhere (a DerivedExprC) is returned as it is."""
+    if isinstance(op, _abi.DerivedExprC):
+        return op
+    return _abi.DerivedExprC(int(DERIVED_OPS.get(op, op)), _abi.MDB_DERIVED_ABS if absolute else 0, a, b, c)
+
+
+def fresh_derived_cells(shape):
+    """Fresh (empty) derived cells: all-zero bytes."""
+    return np.zeros(shape, dtype=DERIVED_CELL_DTYPE)
+
+
+def derived_apply(expr, x, y):
+    """z = f(x, y) element for element on the host (mdb_derived_apply): the evaluator the kernels use, binary32
+    operations in the written order. x and y: float32 arrays of one size; returns float32 of the shape of x."""
+    lib = _abi.load_hip_library()
+    x, y = np.ascontiguousarray(x, dtype=np.float32), np.ascontiguousarray(y, dtype=np.float32)
+    if x.size != y.size:
+        raise ValueError("derived_apply takes two arrays of one size")
+    z = np.empty(x.shape, dtype=np.float32)
+    expr = derived_expr(expr)
+    if lib.mdb_derived_apply(C.byref(expr), x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p), x.size,
+                             z.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return z
+
+
+def derived_merge(into, from_):
+    """into[k] merged with from_[k] in place by the merge rule of mdb_derived_buckets (mdb_derived_merge_n): two arrays
+    of DERIVED_CELL_DTYPE of one size."""
+    lib = _abi.load_hip_library()
+    if into.dtype != DERIVED_CELL_DTYPE or from_.dtype != DERIVED_CELL_DTYPE or into.size != from_.size:
+        raise ValueError("derived_merge takes two cell arrays of one size")
+    if not into.flags.c_contiguous:
+        raise ValueError("derived_merge merges into a contiguous array")
+    from_ = np.ascontiguousarray(from_)
+    if lib.mdb_derived_merge_n(into.ctypes.data_as(C.c_void_p), from_.ctypes.data_as(C.c_void_p), into.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return into
+
+
+def derived_stats(cells):
+    """(count, mean, m2) per cell as an array of MOMENTS_CELL_DTYPE (mdb_derived_stats): what moments_variance takes."""
+    lib = _abi.load_hip_library()
+    if cells.dtype != DERIVED_CELL_DTYPE:
+        raise ValueError("derived_stats takes an array of DERIVED_CELL_DTYPE")
+    flat = np.ascontiguousarray(cells).reshape(-1)
+    out = np.zeros(flat.size, dtype=MOMENTS_CELL_DTYPE)
+    if lib.mdb_derived_stats(flat.ctypes.data_as(C.c_void_p), flat.size, out.ctypes.data_as(C.c_void_p)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out.reshape(cells.shape)
+
+
 EPISODE_DTYPE = np.dtype([("first_row", "<u8"), ("count", "<u8"), ("t_first", "<i8"), ("t_last", "<i8"), ("sum", "<f8"),
                           ("min", "<f4"), ("max", "<f4"), ("group", "<u4"), ("first_segment", "<u4"), ("reserved", "<u8")])
 assert EPISODE_DTYPE.itemsize == C.sizeof(_abi.EpisodeC) == 64
@@ -1381,6 +1443,120 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the data inside the range spans more than one bucket can hold: use comoments_buckets")
         return self.comoments_buckets(x, y, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
+
+    # ---- derived fields of two fields: z = f(x, y) as a column and count, mean, m2, min, max per time bucket ----------
+
+    @staticmethod
+    def _derived_cells(cells, n_groups, n_buckets):
+        if cells is None:
+            return fresh_derived_cells((n_groups, n_buckets))
+        if cells.dtype != DERIVED_CELL_DTYPE or cells.shape != (n_groups, n_buckets) or not cells.flags.c_contiguous:
+            raise ValueError(f"cells must be a contiguous ({n_groups}, {n_buckets}) array of DERIVED_CELL_DTYPE")
+        return cells
+
+    def derived_values(self, x, y, expr, t_lo=None, t_hi=None, timestamps=True):
+        """The generated column z = f(x, y) of two host batches that line up row for row (mdb_derived_values): the rows
+        of grid_batch_range(x, t_lo, t_hi) paired with those of y. Returns (timestamps of x or None, z as float32)."""
+        t_lo = INT64_MIN if t_lo is None else int(t_lo)
+        t_hi = INT64_MAX if t_hi is None else int(t_hi)
+        expr = derived_expr(expr)
+        x_view = x.as_c()
+        y_view = x_view if y is x else y.as_c()
+        n_out = C.c_uint64()
+        self._check(self.lib.mdb_grid_count_range(self.handle, C.byref(x_view), t_lo, t_hi, C.byref(n_out)))
+        capacity = n_out.value
+        out_ts = np.empty(capacity, dtype=np.int64) if timestamps else None
+        out_val = np.empty(capacity, dtype=np.float32)
+        self._check(self.lib.mdb_derived_values(self.handle, C.byref(x_view), C.byref(y_view), C.byref(expr), t_lo, t_hi,
+                                                None if out_ts is None else out_ts.ctypes.data_as(C.c_void_p),
+                                                out_val.ctypes.data_as(C.c_void_p), capacity, C.byref(n_out)))
+        return (None if out_ts is None else out_ts[:n_out.value]), out_val[:n_out.value]
+
+    def derived_values_dev(self, dev_x, dev_y, expr, t_lo, t_hi, out_ts_ptr, out_val_ptr, capacity):
+        """mdb_derived_values_dev on two resident batches into device arrays (out_ts_ptr may be None; out_val_ptr needs
+        4-byte alignment only). Returns the row count."""
+        expr = derived_expr(expr)
+        n_out = C.c_uint64()
+        self._check(self.lib.mdb_derived_values_dev(self.handle, C.byref(dev_x.seg), C.byref(dev_y.seg), C.byref(expr),
+                                                    int(t_lo), int(t_hi), C.c_void_p(out_ts_ptr), C.c_void_p(out_val_ptr),
+                                                    capacity, C.byref(n_out)))
+        return n_out.value
+
+    def derived_buckets(self, x, y, expr, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                        n_groups=None):
+        """The count, mean, m2, min and max of z = f(x, y) per bucket of date_bin(width, ts, origin) and group
+        (mdb_derived_buckets): x and y are two field batches of the same series that line up row for row. Returns
+        `cells` (or fresh ones), shape (n_groups, n_buckets), merged in place. `groups` (per segment of x) and n_groups
+        as for agg_buckets; derived_stats gives what moments_variance takes. `x is y` is uploaded once."""
+        groups = self._groups_array(groups, len(x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._derived_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        expr = derived_expr(expr)
+        x_view = x.as_c()
+        y_view = x_view if y is x else y.as_c()
+        self._check(self.lib.mdb_derived_buckets(self.handle, C.byref(x_view), C.byref(y_view),
+                                                 None if groups is None else groups.ctypes.data_as(C.c_void_p),
+                                                 C.byref(request), C.byref(expr), cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def derived_buckets_list(self, xs, ys, expr, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None, cells=None,
+                             n_groups=None):
+        """Several host batches per field merged as one (mdb_derived_buckets_list): the cuts of xs and ys need not
+        coincide; `groups`: None or one array (or None) per batch of xs."""
+        batch_groups = [None] * len(xs) if groups is None else [self._groups_array(g, len(b))
+                                                                for g, b in zip(groups, xs)]
+        n_groups = self._n_groups(n_groups, cells, batch_groups)
+        cells = self._derived_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        expr = derived_expr(expr)
+        x_views = [batch.as_c() for batch in xs]
+        y_views = x_views if all(a is b for a, b in zip(xs, ys)) and len(xs) == len(ys) else [batch.as_c() for batch in ys]
+        x_pointers = (C.POINTER(_abi.SegmentsC) * max(len(x_views), 1))(*[C.pointer(view) for view in x_views])
+        y_pointers = (C.POINTER(_abi.SegmentsC) * max(len(y_views), 1))(*[C.pointer(view) for view in y_views])
+        group_pointers = (C.c_void_p * max(len(x_views), 1))(
+            *[None if g is None else g.ctypes.data_as(C.c_void_p).value for g in batch_groups])
+        self._check(self.lib.mdb_derived_buckets_list(self.handle, x_pointers, len(x_views), y_pointers, len(y_views),
+                                                      group_pointers, C.byref(request), C.byref(expr),
+                                                      cells.ctypes.data_as(C.c_void_p)))
+        return cells
+
+    def derived_buckets_dev(self, dev_x, dev_y, expr, origin, width, n_buckets, groups=None, t_lo=None, t_hi=None,
+                            cells=None, n_groups=None):
+        """mdb_derived_buckets_dev on two resident batches: `groups` and `cells` are uploaded, the cells downloaded
+        again."""
+        groups = self._groups_array(groups, len(dev_x))
+        n_groups = self._n_groups(n_groups, cells, [groups])
+        cells = self._derived_cells(cells, n_groups, n_buckets)
+        request = self._bucket_request(origin, width, n_buckets, n_groups, t_lo, t_hi, 0)
+        expr = derived_expr(expr)
+        dev_groups = None if groups is None else self.upload_array(groups)
+        dev_cells = self.upload_array(cells)
+        try:
+            self._check(self.lib.mdb_derived_buckets_dev(self.handle, C.byref(dev_x.seg), C.byref(dev_y.seg),
+                                                         None if dev_groups is None else C.c_void_p(dev_groups),
+                                                         C.byref(request), C.byref(expr), C.c_void_p(dev_cells)))
+            cells[...] = self.download_array(dev_cells, cells.size, DERIVED_CELL_DTYPE).reshape(cells.shape)
+        finally:
+            self.dev_free(dev_cells)
+            if dev_groups is not None:
+                self.dev_free(dev_groups)
+        return cells
+
+    def derived(self, x, y, expr, t_lo=None, t_hi=None, groups=None, n_groups=None):
+        """The cells of z = f(x, y) inside [t_lo, t_hi], one per group (shape (n_groups,)): one bucket over the data
+        inside the range, what a whole-batch MIN / MAX / AVG / variance of a generated field needs."""
+        n_groups = self._n_groups(n_groups, None, [self._groups_array(groups, len(x))])
+        if len(x) == 0:
+            return fresh_derived_cells(n_groups)
+        lo, hi = int(np.min(x.start_time)), int(np.max(x.end_time))
+        lo = lo if t_lo is None else max(lo, int(t_lo))
+        hi = hi if t_hi is None else min(hi, int(t_hi))
+        if lo > hi:
+            return fresh_derived_cells(n_groups)
+        if hi - lo + 1 > INT64_MAX:
+            raise ValueError("the data inside the range spans more than one bucket can hold: use derived_buckets")
+        return self.derived_buckets(x, y, expr, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
 
     # ---- linear trend of a field over time: comoments cells with x = the time offset inside the bucket ----------
 

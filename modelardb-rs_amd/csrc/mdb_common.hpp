@@ -103,6 +103,10 @@ enum ScratchSlot {
     SCRATCH_EPISODES_SEGMENTS,   // mdb_episodes*: per segment its rows, first row, summary, prefix, counts and the scans
     SCRATCH_EPISODES_OUT,        // ... the episodes of the host forms before they are copied back
     SCRATCH_INTEGRAL_HEADS,      // mdb_integral_buckets*: the first point's value per segment (the far end of a link)
+    SCRATCH_DERIVED_XCOL,        // mdb_derived_*: the x column: one f32 per row of the x field under the time range
+    SCRATCH_DERIVED_PAIRS,       // ... one slice's row intervals, pair keys, entry counts and offsets, the scan's sums
+    SCRATCH_DERIVED_CHUNKS,      // ... per chunk of one slice's long intervals the pair it belongs to
+    SCRATCH_DERIVED_OUT,         // ... the outputs of mdb_derived_values (host form) before they are copied back
     SCRATCH_SLOT_COUNT
 };
 

@@ -33,7 +33,7 @@ use modelardb_types::types::{ErrorBound, TimestampArray, ValueArray};
 
 pub use sys::{
     mdb_agg_state as AggState, mdb_bucket_request as BucketRequest, mdb_grid_metrics as GridMetrics,
-    mdb_comoments_cell as ComomentsCell, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
+    mdb_comoments_cell as ComomentsCell, mdb_derived_cell as DerivedCell, mdb_derived_expr as DerivedExpr, mdb_hist_request as HistRequest, mdb_m4_cell as M4Cell,
     mdb_episode as Episode, mdb_episodes_request as EpisodesRequest, mdb_moments_cell as MomentsCell,
     mdb_integral_cell as IntegralCell, mdb_integral_request as IntegralRequest,
     mdb_sample_cell as SampleCell, mdb_sample_request as SampleRequest,
@@ -392,6 +392,32 @@ pub fn comoments_moments(cells: &[ComomentsCell], which: u32) -> Result<Vec<Mome
 pub fn comoments_finish(cells: &[ComomentsCell], kind: u32) -> Result<Vec<f64>> {
     let mut out = vec![0.0f64; cells.len()];
     check(unsafe { sys::mdb_comoments_finish(cells.as_ptr(), cells.len() as u64, kind, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// `z[j] = f(x[j], y[j])` by the evaluator the kernels of [`Context::derived_buckets`] use (host arithmetic, no GPU):
+/// binary32 operations in the written order, nothing fused.
+pub fn derived_apply(expr: &DerivedExpr, x: &[f32], y: &[f32]) -> Result<Vec<f32>> {
+    if x.len() != y.len() {
+        return Err(HipError(format!("{} values of x against {} of y", x.len(), y.len())));
+    }
+    let mut z = vec![0.0f32; x.len()];
+    check(unsafe { sys::mdb_derived_apply(expr, x.as_ptr(), y.as_ptr(), x.len() as u64, z.as_mut_ptr()) })?;
+    Ok(z)
+}
+
+/// `into[j]` merged with `from[j]` by the merge rule of [`Context::derived_buckets`] (host arithmetic, no GPU).
+pub fn derived_merge(into: &mut [DerivedCell], from: &[DerivedCell]) -> Result<()> {
+    if into.len() != from.len() {
+        return Err(HipError(format!("{} cells merged into {}", from.len(), into.len())));
+    }
+    check(unsafe { sys::mdb_derived_merge_n(into.as_mut_ptr(), from.as_ptr(), into.len() as u64) })
+}
+
+/// The `(count, mean, m2)` of every cell: what [`moments_variance`] takes (host arithmetic, no GPU).
+pub fn derived_stats(cells: &[DerivedCell]) -> Result<Vec<MomentsCell>> {
+    let mut out = vec![MomentsCell::default(); cells.len()];
+    check(unsafe { sys::mdb_derived_stats(cells.as_ptr(), cells.len() as u64, out.as_mut_ptr()) })?;
     Ok(out)
 }
 
@@ -961,6 +987,81 @@ impl Context {
         check(unsafe {
             sys::mdb_comoments_buckets_list(self.raw(), x_inputs.as_ptr(), x_inputs.len() as u32, y_inputs.as_ptr(),
                                             y_inputs.len() as u32, group_pointers.as_ptr(), request, cells.as_mut_ptr())
+        })
+    }
+
+    /// The generated column `z = f(x, y)` of two fields that line up row for row under `[t_lo, t_hi]` (only the row
+    /// count is checked): where a `GeneratedAsExec` over a `SortedJoinExec` of two fields rebuilds every point of both
+    /// on the host. Returns the timestamps of `x` and `z`.
+    pub fn derived_values(
+        &self,
+        x: &SegmentsView,
+        y: &SegmentsView,
+        expr: &DerivedExpr,
+        t_lo: i64,
+        t_hi: i64,
+    ) -> Result<(Vec<i64>, Vec<f32>)> {
+        let mut rows = 0u64;
+        check(unsafe { sys::mdb_grid_count_range(self.raw(), &x.raw, t_lo, t_hi, &mut rows) })?;
+        let mut timestamps = vec![0i64; rows as usize];
+        let mut values = vec![0.0f32; rows as usize];
+        check(unsafe {
+            sys::mdb_derived_values(self.raw(), &x.raw, &y.raw, expr, t_lo, t_hi, timestamps.as_mut_ptr(),
+                                    values.as_mut_ptr(), rows, &mut rows)
+        })?;
+        timestamps.truncate(rows as usize);
+        values.truncate(rows as usize);
+        Ok((timestamps, values))
+    }
+
+    /// A derived field of two fields per bucket of `date_bin(width, ts, origin)` and group: the count, mean, `m2`, MIN
+    /// and MAX of `z = f(x, y)`. `x` and `y` line up row for row under the request's time range; both are rebuilt
+    /// values-only into device scratch (8 B per row, never copied to the host). `cells` is row-major
+    /// `[n_groups][n_buckets]` (fresh: `DerivedCell::default()`); a cell without pairs stays as it was.
+    /// `request.which_mask` must be 0. [`derived_stats`] gives what [`moments_variance`] takes.
+    pub fn derived_buckets(
+        &self,
+        x: &SegmentsView,
+        y: &SegmentsView,
+        group_of_segment_x: Option<&[u32]>,
+        request: &BucketRequest,
+        expr: &DerivedExpr,
+        cells: &mut [DerivedCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        check_group_ids(x, group_of_segment_x)?;
+        let groups = group_of_segment_x.map_or(std::ptr::null(), |groups| groups.as_ptr());
+        check(unsafe { sys::mdb_derived_buckets(self.raw(), &x.raw, &y.raw, groups, request, expr, cells.as_mut_ptr()) })
+    }
+
+    /// [`Context::derived_buckets`] for several batches per field, merged as one batch per field.
+    pub fn derived_buckets_list(
+        &self,
+        xs: &[SegmentsView],
+        ys: &[SegmentsView],
+        group_of_segment_x: Option<&[Option<&[u32]>]>,
+        request: &BucketRequest,
+        expr: &DerivedExpr,
+        cells: &mut [DerivedCell],
+    ) -> Result<()> {
+        check_bucket_cells(request, cells.len())?;
+        if let Some(groups) = group_of_segment_x {
+            if groups.len() != xs.len() {
+                return Err(HipError(format!("{} group arrays for {} batches", groups.len(), xs.len())));
+            }
+        }
+        let mut group_pointers = Vec::with_capacity(xs.len());
+        for (k, view) in xs.iter().enumerate() {
+            let groups = group_of_segment_x.and_then(|groups| groups[k]);
+            check_group_ids(view, groups)?;
+            group_pointers.push(groups.map_or(std::ptr::null(), |groups| groups.as_ptr()));
+        }
+        let x_inputs: Vec<*const sys::mdb_segments> = xs.iter().map(|view| &view.raw as *const _).collect();
+        let y_inputs: Vec<*const sys::mdb_segments> = ys.iter().map(|view| &view.raw as *const _).collect();
+        check(unsafe {
+            sys::mdb_derived_buckets_list(self.raw(), x_inputs.as_ptr(), x_inputs.len() as u32, y_inputs.as_ptr(),
+                                          y_inputs.len() as u32, group_pointers.as_ptr(), request, expr,
+                                          cells.as_mut_ptr())
         })
     }
 

@@ -268,6 +268,33 @@ pub struct mdb_comoments_cell {
     pub c_xy: f64,
 }
 
+/// The expression of `mdb_derived_*`: `z = f(x, y)`, a generated field of two fields. Every operation is one binary32
+/// operation in the written order; nothing is fused, denormals are kept, the division is the correctly rounded one.
+/// `a`, `b` and `c` must be finite.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_derived_expr {
+    pub op: u32,
+    pub flags: u32,
+    pub a: f32,
+    pub b: f32,
+    pub c: f32,
+}
+
+/// One cell of `mdb_derived_buckets*`: the count, the mean, `m2` (the sum of `(z - mean)^2`) and the extremes of the
+/// generated values of a bucket and group. `count`, `mean`, `m2`: the rules of `mdb_moments_cell`; `min`, `max`: those
+/// of `mdb_agg_buckets`' MIN and MAX. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty, no other member
+/// is read.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_derived_cell {
+    pub count: i64,
+    pub mean: f64,
+    pub m2: f64,
+    pub min: f32,
+    pub max: f32,
+}
+
 /// One episode of `mdb_episodes*`: a maximal run of consecutive passing rows, each but the first continuing its
 /// predecessor (same group, time not stepping back, at most `max_gap` later). 64 bytes.
 #[repr(C)]
@@ -511,6 +538,16 @@ pub const MDB_COMOMENTS_REGR_SLOPE: u32 = 3;
 pub const MDB_COMOMENTS_REGR_INTERCEPT: u32 = 4;
 pub const MDB_COMOMENTS_REGR_R2: u32 = 5;
 
+/// The operations and the flag of `mdb_derived_expr`.
+pub const MDB_DERIVED_LINEAR: u32 = 0; // z = ((a * x) + (b * y)) + c
+pub const MDB_DERIVED_PRODUCT: u32 = 1; // z = (a * (x * y)) + c
+pub const MDB_DERIVED_RATIO: u32 = 2; // z = (a * (x / y)) + c
+pub const MDB_DERIVED_ABS: u32 = 1; // flag: z = |z|
+/// How `mdb_derived_buckets*` cuts the rows: an interval of at most SHORT rows is one lane's, a longer one is cut
+/// into chunks of CHUNK rows, one wave each.
+pub const MDB_DERIVED_SHORT_ROWS: u32 = 64;
+pub const MDB_DERIVED_CHUNK_ROWS: u32 = 1024;
+
 /// One cell of `mdb_moments_buckets*`: the count, the mean and `m2`, the sum of `(v - mean)^2`, of a bucket and group:
 /// the state of DataFusion's variance accumulators. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty,
 /// no other member is read.
@@ -683,6 +720,26 @@ unsafe extern "C" {
     pub fn mdb_comoments_merge_n(into: *mut mdb_comoments_cell, from: *const mdb_comoments_cell, n: u64) -> c_int;
     pub fn mdb_comoments_moments(cells: *const mdb_comoments_cell, n: u64, which: u32, out: *mut mdb_moments_cell) -> c_int;
     pub fn mdb_comoments_finish(cells: *const mdb_comoments_cell, n: u64, kind: u32, out: *mut f64) -> c_int;
+    // ---- derived fields of two fields: z = f(x, y) as a column and per bucket (include/mdb.h) ----
+    pub fn mdb_derived_values_dev(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                                  expr: *const mdb_derived_expr, t_lo: i64, t_hi: i64, timestamps: *mut i64,
+                                  values: *mut f32, capacity: u64, rows_out: *mut u64) -> c_int;
+    pub fn mdb_derived_values(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                              expr: *const mdb_derived_expr, t_lo: i64, t_hi: i64, timestamps: *mut i64,
+                              values: *mut f32, capacity: u64, rows_out: *mut u64) -> c_int;
+    pub fn mdb_derived_buckets(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                               group_of_segment_x: *const u32, request: *const mdb_bucket_request,
+                               expr: *const mdb_derived_expr, inout: *mut mdb_derived_cell) -> c_int;
+    pub fn mdb_derived_buckets_dev(ctx: *mut mdb_ctx, x: *const mdb_segments, y: *const mdb_segments,
+                                   group_of_segment_x: *const u32, request: *const mdb_bucket_request,
+                                   expr: *const mdb_derived_expr, inout: *mut mdb_derived_cell) -> c_int;
+    pub fn mdb_derived_buckets_list(ctx: *mut mdb_ctx, xs: *const *const mdb_segments, n_x: u32,
+                                    ys: *const *const mdb_segments, n_y: u32,
+                                    group_of_segment_x: *const *const u32, request: *const mdb_bucket_request,
+                                    expr: *const mdb_derived_expr, inout: *mut mdb_derived_cell) -> c_int;
+    pub fn mdb_derived_apply(expr: *const mdb_derived_expr, x: *const f32, y: *const f32, n: u64, z: *mut f32) -> c_int;
+    pub fn mdb_derived_merge_n(into: *mut mdb_derived_cell, from: *const mdb_derived_cell, n: u64) -> c_int;
+    pub fn mdb_derived_stats(cells: *const mdb_derived_cell, n: u64, out: *mut mdb_moments_cell) -> c_int;
     // ---- linear trend of a field over time: comoments cells with x = the time offset in the bucket (include/mdb.h) ----
     pub fn mdb_trend_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                              request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
@@ -928,3 +985,15 @@ const _: () = assert!(offset_of!(mdb_comoments_cell, mean_y) == 16);
 const _: () = assert!(offset_of!(mdb_comoments_cell, m2_x) == 24);
 const _: () = assert!(offset_of!(mdb_comoments_cell, m2_y) == 32);
 const _: () = assert!(offset_of!(mdb_comoments_cell, c_xy) == 40);
+const _: () = assert!(size_of::<mdb_derived_expr>() == 20);
+const _: () = assert!(offset_of!(mdb_derived_expr, op) == 0);
+const _: () = assert!(offset_of!(mdb_derived_expr, flags) == 4);
+const _: () = assert!(offset_of!(mdb_derived_expr, a) == 8);
+const _: () = assert!(offset_of!(mdb_derived_expr, b) == 12);
+const _: () = assert!(offset_of!(mdb_derived_expr, c) == 16);
+const _: () = assert!(size_of::<mdb_derived_cell>() == 32);
+const _: () = assert!(offset_of!(mdb_derived_cell, count) == 0);
+const _: () = assert!(offset_of!(mdb_derived_cell, mean) == 8);
+const _: () = assert!(offset_of!(mdb_derived_cell, m2) == 16);
+const _: () = assert!(offset_of!(mdb_derived_cell, min) == 24);
+const _: () = assert!(offset_of!(mdb_derived_cell, max) == 28);
