@@ -649,6 +649,56 @@ int mdb_derived_merge_n(mdb_derived_cell *into, const mdb_derived_cell *from, ui
 /* Host arithmetic, no context, no GPU: out[j] = (count, mean, m2) of cells[j]: what mdb_moments_variance takes. */
 int mdb_derived_stats(const mdb_derived_cell *cells, uint64_t n, mdb_moments_cell *out);
 
+/* Extension: ROLLING WINDOWS over per-bucket cells - moving aggregates:
+ *   a 1-hour moving average every minute, a rolling stddev or correlation, the 15-minute rolling maximum, energy over
+ *   the trailing 24 hours every hour, avg_over_time(x[1h]) at a 1-minute step,
+ *   f(...) OVER (ORDER BY bucket ROWS BETWEEN window-1 PRECEDING AND CURRENT ROW) on a downsampled series.
+ * Every per-bucket operator answers tumbling buckets; a window of `window` buckets of width w is the merge of `window`
+ * adjacent cells. The tumbling cells are computed once by the operator (unchanged) and rolled here with O(1) merges
+ * per window whatever the window's length, in HBM for the _dev form: only the windows need to leave the device.
+ *   request: mdb_roll_request (mdb_format.h): the kind (cell type and merge rule), the view [n_outer][n_buckets][n_inner]
+ *     of the cells, window and stride in buckets.
+ *   Windows: window k of a column (outer, inner) covers the buckets [k * stride, k * stride + window). Only whole
+ *     windows exist: n_windows = n_buckets < window ? 0 : (n_buckets - window) / stride + 1 (mdb_roll_windows). A
+ *     caller who wants trailing windows from its first instant on starts its buckets window - 1 widths earlier.
+ *   out: row-major [n_outer][n_windows][n_inner] cells of the same type. Every cell of it is WRITTEN (not merged into).
+ *   The rule - the ABI promises these bits, not a schedule. With m = window the buckets are cut into blocks of m,
+ *     aligned at multiples of m from bucket 0:
+ *       prefix  P_j[0] = cell[j*m],          P_j[i] = merge(into = P_j[i-1], from = cell[j*m+i])
+ *       suffix  S_j[m-1] = cell[j*m+m-1],    S_j[i] = merge(into = a copy of cell[j*m+i], from = S_j[i+1])
+ *     and for the window that starts at a = k * stride, j = a / m, r = a % m:
+ *       r == 0: out = P_j[m-1] - the plain left fold, byte for byte what chaining the operator's *_merge_n over the m
+ *               cells gives;            otherwise: out = merge(into = S_j[r], from = P_{j+1}[r-1]).
+ *     merge is the operator's existing rule, unchanged: where it has an empty side that side yields the other's bytes,
+ *     and a window over fresh cells only is a fresh cell.
+ *   What follows: integer members are exact in any case. Float members differ from a direct call of the operator with
+ *     buckets of width window * w by rounding only. mdb_roll_cells and mdb_roll_cells_dev agree bit for bit, and so do
+ *     two runs. M4 windows are byte-identical to the direct call (its selection rules do not depend on the order). The
+ *     sign of a zero MIN / MAX follows the left-to-right order of the buckets. MDB_ROLL_U64 adds wrapping. One thing
+ *     is left open, as it is by the merge rules themselves: WHICH NaN a float member holds when it is one - the sign
+ *     and payload are those of the instruction that added or multiplied (x86 makes another NaN of inf - inf than
+ *     gfx950, and of two NaN operands either may come out); that the member is a NaN is part of the promise.
+ *   Trend cells (mdb_trend_buckets*) are mdb_comoments_cell with mean_x relative to the cell's OWN bucket. Before they
+ *     are rolled the caller adds b * width to mean_x of every non-empty cell of bucket b, and subtracts
+ *     k * stride * width from every non-empty window k afterwards (exact in integers below 2^53); m2_x and c_xy, and
+ *     with them slope, r2 and corr, do not depend on the shift.
+ *   _dev: cells and out are in HBM and 8-byte aligned; the two launches (k_roll_suffix - not when stride is a multiple
+ *     of window - and k_roll_windows) are enqueued on the context's stream, and the call returns without waiting for
+ *     them. Scratch: the suffix folds, at most the bytes of the cells. Under mdb_set_scratch_limit a suffix array larger
+ *     than the limit is refused with a message that states the bytes needed: cut the cells by n_outer.
+ *   Errors (mdb_last_error set, out untouched, all found before the device is used): a NULL pointer; an unknown kind; a
+ *     flag bit; window == 0 or stride == 0; n_outer * n_buckets * n_inner * the cell size overflowing 64 bits;
+ *     capacity_cells below n_outer * n_windows * n_inner (the message names the count needed); out overlapping cells;
+ *     _dev: a pointer that is not 8-byte aligned, the scratch refused. Any dimension 0, or n_buckets < window, succeeds
+ *     and writes nothing.
+ * Host arithmetic, no context, no GPU: the number of whole windows. */
+int mdb_roll_windows(const mdb_roll_request *request, uint64_t *n_windows);
+/* Host arithmetic, no context, no GPU: cells and out are host arrays. */
+int mdb_roll_cells(const mdb_roll_request *request, const void *cells, void *out, uint64_t capacity_cells);
+/* Device pointers: cells and out are in HBM. */
+int mdb_roll_cells_dev(mdb_ctx *ctx, const mdb_roll_request *request, const void *cells, void *out,
+                       uint64_t capacity_cells);
+
 /* Extension: value histograms and exact quantiles PER BUCKET of date_bin(width, ts, origin) and group -
  *   SELECT date_bin(...), approx_percentile_cont(field, 0.95) ... GROUP BY 1 / median(field) per bucket / a heat map
  *   (time bucket x value cell),

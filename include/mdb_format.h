@@ -344,6 +344,39 @@ typedef struct mdb_transit_request {    /* 64 bytes, laid out like mdb_change_re
     uint32_t flags;              /* must be 0 */
 } mdb_transit_request;
 
+/* The request of mdb_roll_cells*: overlapping windows of `window` adjacent buckets every `stride` buckets over cells
+ * that a per-bucket operator has made. The cells are viewed as row-major [n_outer][n_buckets][n_inner] - the bucket
+ * axis is the middle one; n_inner is 1 for [group][bucket] cells, the number of value cells (or its square) for the
+ * counters of mdb_hist_buckets, mdb_dwell_buckets and mdb_transit_buckets and for the cells of mdb_binned_buckets. The
+ * kind names the cell type and with it the merge rule, which is the operator's own:
+ *   MDB_ROLL_AGG        mdb_agg_state, 24 B       mdb_agg_buckets*                      (mdb_agg_merge_n)
+ *   MDB_ROLL_M4         mdb_m4_cell, 56 B         mdb_m4_buckets*                       (mdb_m4_merge_n)
+ *   MDB_ROLL_MOMENTS    mdb_moments_cell, 24 B    mdb_moments_buckets*, mdb_binned_buckets*   (mdb_moments_merge_n)
+ *   MDB_ROLL_COMOMENTS  mdb_comoments_cell, 48 B  mdb_comoments_buckets*, mdb_trend_buckets*  (mdb_comoments_merge_n)
+ *   MDB_ROLL_DERIVED    mdb_derived_cell, 32 B    mdb_derived_buckets*                  (mdb_derived_merge_n)
+ *   MDB_ROLL_INTEGRAL   mdb_integral_cell, 16 B   mdb_integral_buckets*                 (mdb_integral_merge_n)
+ *   MDB_ROLL_CHANGE     mdb_change_cell, 64 B     mdb_change_buckets*                   (mdb_change_merge_n)
+ *   MDB_ROLL_U64        uint64_t, 8 B             mdb_hist_buckets*, mdb_dwell_buckets*, mdb_transit_buckets* (wrapping add)
+ * mdb_sample_cell has no kind: its cells belong to instants, not to intervals, and a window of instants is not the
+ * merge of its instants' cells in any sense a query asks for. */
+#define MDB_ROLL_AGG       0u
+#define MDB_ROLL_M4        1u
+#define MDB_ROLL_MOMENTS   2u
+#define MDB_ROLL_COMOMENTS 3u
+#define MDB_ROLL_DERIVED   4u
+#define MDB_ROLL_INTEGRAL  5u
+#define MDB_ROLL_CHANGE    6u
+#define MDB_ROLL_U64       7u
+typedef struct mdb_roll_request {       /* 48 bytes */
+    uint32_t kind;       /* MDB_ROLL_* */
+    uint32_t flags;      /* must be 0 */
+    uint64_t n_outer;
+    uint64_t n_buckets;
+    uint64_t n_inner;
+    uint64_t window;     /* buckets per window, >= 1 */
+    uint64_t stride;     /* buckets between the starts of two windows, >= 1 */
+} mdb_roll_request;
+
 /* One series chunk of mdb_compress_chunk_list: n sorted data points in two arrays of the caller. */
 typedef struct mdb_chunk {
     const int64_t *ts;
@@ -502,5 +535,13 @@ MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, buckets) == 0);
 MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, max_gap) == 48);
 MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, reserved) == 56);
 MDB_LAYOUT_ASSERT(offsetof(mdb_transit_request, flags) == 60);
+MDB_LAYOUT_ASSERT(sizeof(mdb_roll_request) == 48);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, kind) == 0);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, flags) == 4);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, n_outer) == 8);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, n_buckets) == 16);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, n_inner) == 24);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, window) == 32);
+MDB_LAYOUT_ASSERT(offsetof(mdb_roll_request, stride) == 40);
 
 #endif /* MDB_FORMAT_H */

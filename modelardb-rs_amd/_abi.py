@@ -396,6 +396,30 @@ class DerivedCellC(C.Structure):
     ]
 
 
+MDB_ROLL_AGG = 0         # mdb_agg_state, 24 B
+MDB_ROLL_M4 = 1          # mdb_m4_cell, 56 B
+MDB_ROLL_MOMENTS = 2     # mdb_moments_cell, 24 B (also binned)
+MDB_ROLL_COMOMENTS = 3   # mdb_comoments_cell, 48 B (also trend)
+MDB_ROLL_DERIVED = 4     # mdb_derived_cell, 32 B
+MDB_ROLL_INTEGRAL = 5    # mdb_integral_cell, 16 B
+MDB_ROLL_CHANGE = 6      # mdb_change_cell, 64 B
+MDB_ROLL_U64 = 7         # uint64_t, wrapping add (hist_buckets, dwell, transit)
+
+
+class RollRequestC(C.Structure):
+    """mdb_roll_request: windows of `window` adjacent buckets every `stride` buckets over cells viewed as row-major
+    [n_outer][n_buckets][n_inner] (mdb_roll_cells*)."""
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("n_outer", C.c_uint64),
+        ("n_buckets", C.c_uint64),
+        ("n_inner", C.c_uint64),
+        ("window", C.c_uint64),
+        ("stride", C.c_uint64),
+    ]
+
+
 class HistRequestC(C.Structure):
     """mdb_hist_request: the time range, number of edges and number of groups of mdb_hist_batch*."""
     _fields_ = [
@@ -518,6 +542,9 @@ _HIP_SYMBOLS = {
     "mdb_derived_apply": (C.c_int, [C.POINTER(DerivedExprC), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "mdb_derived_merge_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_derived_stats": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "mdb_roll_windows": (C.c_int, [C.POINTER(RollRequestC), C.POINTER(C.c_uint64)]),
+    "mdb_roll_cells": (C.c_int, [C.POINTER(RollRequestC), C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mdb_roll_cells_dev": (C.c_int, [C.c_void_p, C.POINTER(RollRequestC), C.c_void_p, C.c_void_p, C.c_uint64]),
     "mdb_trend_buckets": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),
                                     C.c_void_p]),
     "mdb_trend_buckets_dev": (C.c_int, [C.c_void_p, C.POINTER(SegmentsC), C.c_void_p, C.POINTER(BucketRequestC),

@@ -452,6 +452,69 @@ def change_finish(cells, kind):
     return out.reshape(cells.shape)
 
 
+# The kinds of mdb_roll_request (MDB_ROLL_*) and the numpy type of their cells: the cell type names the merge rule.
+MDB_ROLL_AGG, MDB_ROLL_M4, MDB_ROLL_MOMENTS, MDB_ROLL_COMOMENTS = (_abi.MDB_ROLL_AGG, _abi.MDB_ROLL_M4, _abi.MDB_ROLL_MOMENTS,
+                                                                  _abi.MDB_ROLL_COMOMENTS)
+MDB_ROLL_DERIVED, MDB_ROLL_INTEGRAL, MDB_ROLL_CHANGE, MDB_ROLL_U64 = (_abi.MDB_ROLL_DERIVED, _abi.MDB_ROLL_INTEGRAL,
+                                                                      _abi.MDB_ROLL_CHANGE, _abi.MDB_ROLL_U64)
+ROLL_KINDS = {
+    MDB_ROLL_AGG: AGG_STATE_DTYPE,              # agg_buckets*
+    MDB_ROLL_M4: M4_CELL_DTYPE,                 # m4_buckets*
+    MDB_ROLL_MOMENTS: MOMENTS_CELL_DTYPE,       # moments_buckets*, binned_buckets*
+    MDB_ROLL_COMOMENTS: COMOMENTS_CELL_DTYPE,   # comoments_buckets*, trend_buckets*
+    MDB_ROLL_DERIVED: DERIVED_CELL_DTYPE,       # derived_buckets*
+    MDB_ROLL_INTEGRAL: INTEGRAL_CELL_DTYPE,     # integral_buckets*
+    MDB_ROLL_CHANGE: CHANGE_CELL_DTYPE,         # change_buckets*
+    MDB_ROLL_U64: np.dtype("<u8"),              # hist_buckets*, dwell_buckets*, transit_buckets*: wrapping add
+}
+
+
+def roll_windows(n_buckets, window, stride=1):
+    """The number of whole windows of `window` buckets every `stride` buckets in `n_buckets` buckets
+    (mdb_roll_windows): 0 when n_buckets < window, else (n_buckets - window) // stride + 1."""
+    lib = _abi.load_hip_library()
+    request = _abi.RollRequestC(MDB_ROLL_U64, 0, 1, int(n_buckets), 1, int(window), int(stride))
+    n_windows = C.c_uint64()
+    if lib.mdb_roll_windows(C.byref(request), C.byref(n_windows)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return n_windows.value
+
+
+def roll_kind_of(dtype):
+    """The MDB_ROLL_* kind whose cells have the numpy type `dtype`."""
+    for kind, cell_dtype in ROLL_KINDS.items():
+        if dtype == cell_dtype:
+            return kind
+    raise ValueError(f"no MDB_ROLL_* kind has cells of type {dtype}: see ROLL_KINDS (sample cells do not roll)")
+
+
+def roll_cells(cells, window, stride=1, kind=None):
+    """Rolling windows over the cells of a per-bucket operator, on the host (mdb_roll_cells): axis 1 of `cells` is the
+    bucket axis, the axes behind it are taken as one (n_inner), a 1-D array is one column. Window k is the merge of
+    the buckets [k * stride, k * stride + window) by the operator's own merge rule in the fixed order mdb.h states,
+    so Context.roll_cells_dev gives the same bytes. `kind` (MDB_ROLL_*) defaults to the one of the array's type.
+    Returns the windows with axis 1 of length roll_windows(n_buckets, window, stride)."""
+    lib = _abi.load_hip_library()
+    cells = np.ascontiguousarray(cells)
+    kind = roll_kind_of(cells.dtype) if kind is None else int(kind)
+    if kind in ROLL_KINDS and cells.dtype != ROLL_KINDS[kind]:
+        raise ValueError(f"kind {kind} rolls cells of type {ROLL_KINDS[kind]}")
+    if cells.ndim == 0:
+        raise ValueError("roll_cells takes an array with a bucket axis")
+    shape = (1, cells.shape[0]) if cells.ndim == 1 else cells.shape
+    n_outer, n_buckets = shape[0], shape[1]
+    n_inner = int(np.prod(shape[2:], dtype=np.int64))
+    request = _abi.RollRequestC(kind, 0, n_outer, n_buckets, n_inner, int(window), int(stride))
+    n_windows = C.c_uint64()
+    if lib.mdb_roll_windows(C.byref(request), C.byref(n_windows)) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    out_shape = (n_windows.value,) if cells.ndim == 1 else (n_outer, n_windows.value) + tuple(shape[2:])
+    out = np.zeros(out_shape, dtype=cells.dtype)
+    if lib.mdb_roll_cells(C.byref(request), cells.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), out.size) != 0:
+        raise HipError(lib.mdb_last_error().decode())
+    return out
+
+
 def _f64_key(x):
     """IEEE 754 totalOrder key of an f64 bit pattern (signed integer comparison)."""
     bits = struct.unpack("<q", struct.pack("<d", x))[0]
@@ -692,8 +755,9 @@ class Context:
         return released.value
 
     def set_scratch_limit(self, nbytes):
-        """Device scratch beyond `nbytes` is given back after every call (0: keep everything). Only comoments_buckets*
-        is refused for it: when its y column alone (4 B per row) is larger."""
+        """Device scratch beyond `nbytes` is given back after every call (0: keep everything). Refused for it are the
+        calls whose one array alone is larger: the value columns of comoments_buckets* and derived_* (4 B per row each)
+        and the suffix folds of roll_cells_dev (at most the bytes of its cells)."""
         self._check(self.lib.mdb_set_scratch_limit(self.handle, C.c_uint64(nbytes)))
 
     # ---- device memory -----------------------------------------------------------------------
@@ -1557,6 +1621,19 @@ class Context:
         if hi - lo + 1 > INT64_MAX:
             raise ValueError("the data inside the range spans more than one bucket can hold: use derived_buckets")
         return self.derived_buckets(x, y, expr, lo, hi - lo + 1, 1, groups, lo, hi, None, n_groups).reshape(n_groups)
+
+    # ---- rolling windows over per-bucket cells: moving aggregates -------------------------------------------------
+
+    def roll_cells_dev(self, kind, cells_ptr, n_outer, n_buckets, n_inner, window, stride, out_ptr, capacity):
+        """mdb_roll_cells_dev: the cells [n_outer][n_buckets][n_inner] at `cells_ptr` (HBM, 8-byte aligned) rolled into
+        [n_outer][n_windows][n_inner] cells at `out_ptr` (HBM, room for `capacity` cells), enqueued on the context's
+        stream: the bytes roll_cells gives. Returns the number of windows per column."""
+        request = _abi.RollRequestC(int(kind), 0, int(n_outer), int(n_buckets), int(n_inner), int(window), int(stride))
+        self._check(self.lib.mdb_roll_cells_dev(self.handle, C.byref(request), C.c_void_p(cells_ptr), C.c_void_p(out_ptr),
+                                                int(capacity)))
+        n_windows = C.c_uint64()
+        self._check(self.lib.mdb_roll_windows(C.byref(request), C.byref(n_windows)))
+        return n_windows.value
 
     # ---- linear trend of a field over time: comoments cells with x = the time offset inside the bucket ----------
 

@@ -20,6 +20,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>
 
+#include "mdb_agg_merge.hpp"
 #include "mdb_common.hpp"
 
 namespace mdb {
@@ -83,15 +84,8 @@ static const Rccl *rccl() {
             return ::mdb::fail(std::string(#expr) + ": " + nccl->get_error_string(mdb_nccl_));    \
     } while (0)
 
-// Fold `from` into `into` exactly as the accumulators fold a batch into their state
-// (model_simple_aggregates.rs:355 count, :398-401 min, :441-444 max, :501-510 sum): NaN partial
-// extrema are skipped the way f32::min / f32::max skip them.
-void merge_agg_state(mdb_agg_state *into, const mdb_agg_state &from) {
-    into->sum += from.sum;
-    into->count += from.count;
-    if (!(from.min != from.min) && (into->min != into->min || from.min < into->min)) into->min = from.min;
-    if (!(from.max != from.max) && (into->max != into->max || from.max > into->max)) into->max = from.max;
-}
+// The rule is agg_state_merge (mdb_agg_merge.hpp): ONE rule for this file, the host and the rolling-window kernels.
+void merge_agg_state(mdb_agg_state *into, const mdb_agg_state &from) { agg_state_merge(*into, from); }
 
 } // namespace mdb
 

@@ -107,6 +107,7 @@ enum ScratchSlot {
     SCRATCH_DERIVED_PAIRS,       // ... one slice's row intervals, pair keys, entry counts and offsets, the scan's sums
     SCRATCH_DERIVED_CHUNKS,      // ... per chunk of one slice's long intervals the pair it belongs to
     SCRATCH_DERIVED_OUT,         // ... the outputs of mdb_derived_values (host form) before they are copied back
+    SCRATCH_ROLL_SUFFIX,         // mdb_roll_cells_dev: the right-to-left folds S of every block but a column's last
     SCRATCH_SLOT_COUNT
 };
 

@@ -40,12 +40,17 @@ pub use sys::{
     mdb_change_cell as ChangeCell, mdb_change_request as ChangeRequest,
     mdb_dwell_request as DwellRequest,
     mdb_transit_request as TransitRequest,
+    mdb_roll_request as RollRequest,
     mdb_value_filter as ValueFilter,
 };
 pub use sys::{MDB_INTEGRAL_LINEAR, MDB_INTEGRAL_STEP};
 pub use sys::{MDB_SAMPLE_EXACT, MDB_SAMPLE_LINEAR, MDB_SAMPLE_STEP};
 pub use sys::{MDB_CHANGE_INCREASE, MDB_CHANGE_NET, MDB_CHANGE_RATE, MDB_CHANGE_VARIATION};
 pub use sys::MDB_DWELL_STEP;
+pub use sys::{
+    MDB_ROLL_AGG, MDB_ROLL_CHANGE, MDB_ROLL_COMOMENTS, MDB_ROLL_DERIVED, MDB_ROLL_INTEGRAL, MDB_ROLL_M4, MDB_ROLL_MOMENTS,
+    MDB_ROLL_U64,
+};
 pub use sys::{MDB_HIST_MAX_EDGES, MDB_QUANTILE_BUCKETS_MAX_Q, MDB_QUANTILE_BUCKETS_PASSES};
 pub use sys::{MDB_VALUE_HI_OPEN, MDB_VALUE_LO_OPEN, MDB_VALUE_NO_HI, MDB_VALUE_NO_LO};
 pub use sys::{MDB_MASK_AND, MDB_MASK_ANDNOT, MDB_MASK_NOT, MDB_MASK_OR, MDB_MASK_XOR};
@@ -418,6 +423,66 @@ pub fn derived_merge(into: &mut [DerivedCell], from: &[DerivedCell]) -> Result<(
 pub fn derived_stats(cells: &[DerivedCell]) -> Result<Vec<MomentsCell>> {
     let mut out = vec![MomentsCell::default(); cells.len()];
     check(unsafe { sys::mdb_derived_stats(cells.as_ptr(), cells.len() as u64, out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// A cell type that [`roll_cells`] can roll: its `MDB_ROLL_*` kind names the merge rule.
+pub trait RollCell: Copy {
+    const KIND: u32;
+}
+impl RollCell for AggState {
+    const KIND: u32 = MDB_ROLL_AGG;
+}
+impl RollCell for M4Cell {
+    const KIND: u32 = MDB_ROLL_M4;
+}
+/// (also the cells of `mdb_binned_buckets*`)
+impl RollCell for MomentsCell {
+    const KIND: u32 = MDB_ROLL_MOMENTS;
+}
+/// (also the cells of `mdb_trend_buckets*`)
+impl RollCell for ComomentsCell {
+    const KIND: u32 = MDB_ROLL_COMOMENTS;
+}
+impl RollCell for DerivedCell {
+    const KIND: u32 = MDB_ROLL_DERIVED;
+}
+impl RollCell for IntegralCell {
+    const KIND: u32 = MDB_ROLL_INTEGRAL;
+}
+impl RollCell for ChangeCell {
+    const KIND: u32 = MDB_ROLL_CHANGE;
+}
+/// The counters of `mdb_hist_buckets*`, `mdb_dwell_buckets*` and `mdb_transit_buckets*`: wrapping add.
+impl RollCell for u64 {
+    const KIND: u32 = MDB_ROLL_U64;
+}
+
+/// The number of whole windows of `window` buckets every `stride` buckets in `n_buckets` buckets (host arithmetic).
+pub fn roll_windows(n_buckets: u64, window: u64, stride: u64) -> Result<u64> {
+    let request = RollRequest { kind: MDB_ROLL_U64, flags: 0, n_outer: 1, n_buckets, n_inner: 1, window, stride };
+    let mut n_windows = 0u64;
+    check(unsafe { sys::mdb_roll_windows(&request, &mut n_windows) })?;
+    Ok(n_windows)
+}
+
+/// Rolling windows over the cells of a per-bucket operator (host arithmetic, no GPU): `cells` is row-major
+/// `[n_outer][n_buckets][n_inner]`, the result `[n_outer][n_windows][n_inner]`; window `k` is the merge of the buckets
+/// `[k * stride, k * stride + window)` by the operator's merge rule, in the fixed order `mdb.h` states.
+pub fn roll_cells<C: RollCell>(cells: &[C], n_outer: u64, n_buckets: u64, n_inner: u64, window: u64, stride: u64)
+                               -> Result<Vec<C>> {
+    let request = RollRequest { kind: C::KIND, flags: 0, n_outer, n_buckets, n_inner, window, stride };
+    let n_windows = roll_windows(n_buckets, window, stride)?;
+    let expected = n_outer.checked_mul(n_buckets).and_then(|n| n.checked_mul(n_inner));
+    if expected != Some(cells.len() as u64) {
+        return Err(HipError(format!("{} cells for [{n_outer}][{n_buckets}][{n_inner}]", cells.len())));
+    }
+    let n_out = (n_outer * n_windows * n_inner) as usize;
+    if n_out == 0 {
+        return Ok(Vec::new());
+    }
+    let mut out = vec![cells[0]; n_out];
+    check(unsafe { sys::mdb_roll_cells(&request, cells.as_ptr().cast(), out.as_mut_ptr().cast(), n_out as u64) })?;
     Ok(out)
 }
 

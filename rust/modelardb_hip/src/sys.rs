@@ -295,6 +295,20 @@ pub struct mdb_derived_cell {
     pub max: f32,
 }
 
+/// The request of `mdb_roll_cells*`: windows of `window` adjacent buckets every `stride` buckets over cells viewed as
+/// row-major `[n_outer][n_buckets][n_inner]`; `kind` (`MDB_ROLL_*`) names the cell type and its merge rule. 48 bytes.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct mdb_roll_request {
+    pub kind: u32,
+    pub flags: u32,
+    pub n_outer: u64,
+    pub n_buckets: u64,
+    pub n_inner: u64,
+    pub window: u64,
+    pub stride: u64,
+}
+
 /// One episode of `mdb_episodes*`: a maximal run of consecutive passing rows, each but the first continuing its
 /// predecessor (same group, time not stepping back, at most `max_gap` later). 64 bytes.
 #[repr(C)]
@@ -548,6 +562,17 @@ pub const MDB_DERIVED_ABS: u32 = 1; // flag: z = |z|
 pub const MDB_DERIVED_SHORT_ROWS: u32 = 64;
 pub const MDB_DERIVED_CHUNK_ROWS: u32 = 1024;
 
+/// The kinds of `mdb_roll_request`: the cell type and with it the merge rule. (`mdb_sample_cell` has none: instants
+/// are not intervals.)
+pub const MDB_ROLL_AGG: u32 = 0; // mdb_agg_state, 24 B
+pub const MDB_ROLL_M4: u32 = 1; // mdb_m4_cell, 56 B
+pub const MDB_ROLL_MOMENTS: u32 = 2; // mdb_moments_cell, 24 B (also binned)
+pub const MDB_ROLL_COMOMENTS: u32 = 3; // mdb_comoments_cell, 48 B (also trend)
+pub const MDB_ROLL_DERIVED: u32 = 4; // mdb_derived_cell, 32 B
+pub const MDB_ROLL_INTEGRAL: u32 = 5; // mdb_integral_cell, 16 B
+pub const MDB_ROLL_CHANGE: u32 = 6; // mdb_change_cell, 64 B
+pub const MDB_ROLL_U64: u32 = 7; // u64, wrapping add (hist_buckets, dwell, transit)
+
 /// One cell of `mdb_moments_buckets*`: the count, the mean and `m2`, the sum of `(v - mean)^2`, of a bucket and group:
 /// the state of DataFusion's variance accumulators. A fresh cell is all-zero bytes (`Default`); `count == 0`: empty,
 /// no other member is read.
@@ -740,6 +765,12 @@ unsafe extern "C" {
     pub fn mdb_derived_apply(expr: *const mdb_derived_expr, x: *const f32, y: *const f32, n: u64, z: *mut f32) -> c_int;
     pub fn mdb_derived_merge_n(into: *mut mdb_derived_cell, from: *const mdb_derived_cell, n: u64) -> c_int;
     pub fn mdb_derived_stats(cells: *const mdb_derived_cell, n: u64, out: *mut mdb_moments_cell) -> c_int;
+    // ---- rolling windows over per-bucket cells: moving aggregates (include/mdb.h) ----
+    pub fn mdb_roll_windows(request: *const mdb_roll_request, n_windows: *mut u64) -> c_int;
+    pub fn mdb_roll_cells(request: *const mdb_roll_request, cells: *const c_void, out: *mut c_void,
+                          capacity_cells: u64) -> c_int;
+    pub fn mdb_roll_cells_dev(ctx: *mut mdb_ctx, request: *const mdb_roll_request, cells: *const c_void,
+                              out: *mut c_void, capacity_cells: u64) -> c_int;
     // ---- linear trend of a field over time: comoments cells with x = the time offset in the bucket (include/mdb.h) ----
     pub fn mdb_trend_buckets(ctx: *mut mdb_ctx, input: *const mdb_segments, group_of_segment: *const u32,
                              request: *const mdb_bucket_request, inout: *mut mdb_comoments_cell) -> c_int;
@@ -997,3 +1028,11 @@ const _: () = assert!(offset_of!(mdb_derived_cell, mean) == 8);
 const _: () = assert!(offset_of!(mdb_derived_cell, m2) == 16);
 const _: () = assert!(offset_of!(mdb_derived_cell, min) == 24);
 const _: () = assert!(offset_of!(mdb_derived_cell, max) == 28);
+const _: () = assert!(size_of::<mdb_roll_request>() == 48);
+const _: () = assert!(offset_of!(mdb_roll_request, kind) == 0);
+const _: () = assert!(offset_of!(mdb_roll_request, flags) == 4);
+const _: () = assert!(offset_of!(mdb_roll_request, n_outer) == 8);
+const _: () = assert!(offset_of!(mdb_roll_request, n_buckets) == 16);
+const _: () = assert!(offset_of!(mdb_roll_request, n_inner) == 24);
+const _: () = assert!(offset_of!(mdb_roll_request, window) == 32);
+const _: () = assert!(offset_of!(mdb_roll_request, stride) == 40);
